@@ -17,8 +17,8 @@ The exchange overlaps the assembly: the ghost rows are formed first and travel w
 against a single-part assembly of a sampled sub-brick around a corner it shares with its neighbours.  torch.distributed
 (gloo) only carries the rendezvous, the one-off exchange lists and the timing reduction.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under torch.distributed.run.
-Prints ONE JSON line on rank 0.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]; for N > 1 under torch.distributed.run.
+Prints ONE JSON line on rank 0; its `ms_per_step` is the wall time of one of the K timed steps.
 """
 import argparse
 import json
@@ -91,6 +91,40 @@ def cpu_baseline(n, nthreads):
     dt = time.perf_counter() - t0
     assert rc == 0
     return len(conn) / dt, orc, (u, p, z, zp), ls, xi
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of each dumped array: 7 arrays x 8 MB (float64) stay under 64 MB
+DUMP_SEED = 20240917
+
+
+def dump_outputs(case, out_dir):
+    """--dump-outputs: what the last timed step handed its caller -- the CSR values of A00 A01 A10 A11, b0, b1 (this rank's
+    linear system; assembly accumulates into it, so it holds the sum of the W + K steps) and the local state xi -- as
+    DIR/<name>.npy in float64.  An array of more than DUMP_SAMPLE entries is reduced to the entries at a fixed, seeded set
+    of flat positions (sorted).  stats.npy holds, per array in the order of `names`, the L1 norm, L2 norm, min and max of
+    the WHOLE array.  Returns what was written, for the result line."""
+    import torch
+    ls = case.ls
+    arrays = [("A%d%d" % (i, j), ls.A[i][j]) for i in range(2) for j in range(2)]
+    arrays += [("b%d" % i, ls.b[i]) for i in range(2)] + [("xi", case.xi.reshape(-1))]
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    written, stats = {}, []
+    for name, t in arrays:
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+            a = t[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        stats.append([float(torch.linalg.vector_norm(t, 1)), float(torch.linalg.vector_norm(t, 2)), float(t.min()), float(t.max())]
+                     if n else [0.0] * 4)
+        written[name] = {"entries": n, "dumped": int(a.size)}
+    np.save(os.path.join(out_dir, "stats.npy"), np.array(stats, dtype=np.float64))
+    total = sum(os.path.getsize(os.path.join(out_dir, k + ".npy")) for k in list(written) + ["stats"])
+    assert total <= 64 << 20, total
+    return {"dir": out_dir, "names": [k for k, _ in arrays], "arrays": written, "bytes": total, "sample_seed": DUMP_SEED}
 
 
 def consistent_fields(X, extent, eps=0.004, E=1000.0, nu=0.25):
@@ -414,7 +448,12 @@ def main():
                     help="rccl (default): grouped ncclSend/ncclRecv over xGMI, one rank per GPU; host: rehearsal of the N > 1 "
                          "path with all ranks on one GPU (RCCL refuses that), messages through the host")
     ap.add_argument("--require-rccl", action="store_true", help="N > 1: exit non-zero instead of falling back to the host transport when the RCCL communicator fails")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned (rank 0's linear system and local state, "
+                         "a fixed seeded sample of each large array) as DIR/<name>.npy; see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.transport = {"nccl": "rccl", "gloo": "host"}.get(args.transport, args.transport)
 
     import torch
@@ -477,6 +516,7 @@ def main():
         scalings = ["weak"]
     head = Case(args, scalings[0], world, rank, dist, dev, comm)
     res = head.run(args.steps, args.warmup)
+    dumped = dump_outputs(head, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     asm = head.asm
     reps = max(2, min(5, args.steps))
     also = {}
@@ -561,6 +601,8 @@ def main():
                                 "mean / median / max, min over ranks of the min); ms_per_step above is the whole step: kernel + C1 + C2 for N > 1"},
         "also": also,
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if fallback:
         out["transport_fallback"] = fallback  # NOT an RCCL measurement: the messages went through the host
     nnz_total = sum(asm.nnz[i][j] for i in range(2) for j in range(2))

@@ -83,23 +83,23 @@ def test_product_does_not_reference_the_oracle_or_emulator():
 
 
 # ---- compiled clients of include/c8.h (tests/abi_client): the boundary without ctypes -------------------------------------
-ABI_OUT = "/tmp/c8_abi_client"
-
-
-def _build_abi_clients():
+@pytest.fixture(scope="module")
+def abi_out(tmp_path_factory):
+    """the clients, built afresh for this session into its own temporary directory (they link this checkout's libc8.so)"""
     import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "abi_client"), "-s", "OUT=" + ABI_OUT])
+    out = str(tmp_path_factory.mktemp("c8_abi_client"))
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "abi_client"), "-s", "OUT=" + out])
+    return out
 
 
-def test_header_compiles_as_c_and_cpp_and_matches_the_ctypes_mirror():
+def test_header_compiles_as_c_and_cpp_and_matches_the_ctypes_mirror(abi_out):
     """include/c8.h compiled by gcc -std=c11 and g++ -std=c++17 (-pedantic -Werror): sizeof / offsetof of every struct and
     the enum values, compared with calibr8_amd/lib.py -- the layouts every GPU test relies on through ctypes."""
     import json
     import subprocess
     from calibr8_amd import lib
-    _build_abi_clients()
-    c_layout = json.loads(subprocess.check_output([os.path.join(ABI_OUT, "layout_c")]))
-    cpp_layout = json.loads(subprocess.check_output([os.path.join(ABI_OUT, "layout_cpp")]))
+    c_layout = json.loads(subprocess.check_output([os.path.join(abi_out, "layout_c")]))
+    cpp_layout = json.loads(subprocess.check_output([os.path.join(abi_out, "layout_cpp")]))
     assert c_layout == cpp_layout
     mirror = {"c8_mesh_desc": lib.MeshDesc, "c8_model_desc": lib.ModelDesc, "c8_state": lib.State, "c8_system": lib.System,
               "c8_calibration_desc": lib.CalibrationDesc, "c8_dbc": lib.Dbc, "c8_tbc": lib.Tbc, "c8_newton_opts": lib.NewtonOpts,
@@ -116,21 +116,20 @@ def test_header_compiles_as_c_and_cpp_and_matches_the_ctypes_mirror():
     for k, v in c_layout["enums"].items():
         assert getattr(lib, k) == v, k
     # the clients that run on the GPU box link against libc8.so here (no device needed to link)
-    assert os.path.exists(os.path.join(ABI_OUT, "client_c")) and os.path.exists(os.path.join(ABI_OUT, "client_cpp"))
+    assert os.path.exists(os.path.join(abi_out, "client_c")) and os.path.exists(os.path.join(abi_out, "client_cpp"))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("binary", ["client_c", "client_cpp"])
-def test_compiled_client_matches_the_python_path_bitwise(binary, tmp_path):
+def test_compiled_client_matches_the_python_path_bitwise(binary, tmp_path, abi_out):
     """tests/abi_client/abi_client.c (C11 and C++17 builds): c8_create -> c8_assemble_forward_jacobian (twice) ->
     c8_assemble_residual -> c8_halo_build / attach / gather / scatter_x -> c8_comm_allreduce_sum, straight through the C ABI;
     the same inputs through calibr8_amd.Assembler give the same bits."""
     import subprocess
     import torch
     import calibr8_amd
-    _build_abi_clients()
     out = str(tmp_path / "abi.bin")
-    msg = subprocess.check_output([os.path.join(ABI_OUT, binary), out]).decode()
+    msg = subprocess.check_output([os.path.join(abi_out, binary), out]).decode()
     assert msg.startswith("abi_client ok")
     raw = np.fromfile(out)
     nnodes, nelems = int(raw[0]), int(raw[1])
