@@ -254,6 +254,33 @@ class Assembler:
         return self._rc(self.L.c8_param_gradient(self.h, C.byref(st), z, C.c_void_p(phi.data_ptr()),
                                                  C.c_void_p(grad.data_ptr())))
 
+    # ---- virtual fields method (one-residual systems; calibr8_amd.vfm.VFMProblem drives these) ----------------------
+    def vfm_set_virtual_field(self, w):
+        """nodal virtual field [nnodes * ndims] (device tensor, kept by reference)"""
+        self._vfm_w = w
+        _l.check(self.L.c8_vfm_set_virtual_field(self.h, C.c_void_p(w.data_ptr())))
+
+    def vfm_internal_power(self, u, p, u_prev, p_prev, xi_prev, xi, ivw, b=None):
+        """eval_measured_residual: local solve with the measured u, u_prev into xi; ivw (device, one double) += w^T R;
+        b (device [nnodes * ndims] or None) += R.  Returns 0, or -1 if a local solve failed."""
+        st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
+        return self._rc(self.L.c8_vfm_internal_power(self.h, C.byref(st), None if b is None else C.c_void_p(b.data_ptr()),
+                                                     C.c_void_p(ivw.data_ptr())))
+
+    def vfm_forward_sens(self, u, p, u_prev, p_prev, xi_prev, xi, S_prev, S, ivw, divw):
+        """eval_measured_residual_and_grad: as vfm_internal_power, S = local sensitivities [elems][pts][nloc][n_active]
+        from S_prev (None = 0), divw [n_active] += d(w^T R)/dp"""
+        st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
+        return self._rc(self.L.c8_vfm_forward_sens(self.h, C.byref(st), None if S_prev is None else C.c_void_p(S_prev.data_ptr()),
+                                                   C.c_void_p(S.data_ptr()), C.c_void_p(ivw.data_ptr()),
+                                                   C.c_void_p(divw.data_ptr())))
+
+    def vfm_adjoint_step(self, u, p, u_prev, p_prev, xi_prev, xi, c, h, grad):
+        """eval_vfm_adjoint_gradient at the stored state: h [elems][pts][nloc] updated in place, grad [n_active] +="""
+        st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
+        return self._rc(self.L.c8_vfm_adjoint_step(self.h, C.byref(st), float(c), C.c_void_p(h.data_ptr()),
+                                                   C.c_void_p(grad.data_ptr())))
+
     # ---- next to the hot path: boundary conditions on the device system, y = A x ----------------------
     def apply_dirichlet(self, dbcs, x_u, x_p, ls, is_adjoint=False):
         """dbcs: list of (resid, eq, nodes int32 device tensor, values float64 device tensor)."""

@@ -83,6 +83,10 @@ struct c8_ctx {
   int async = 0;
   int32_t const* subset = nullptr;   // set for the duration of a *_subset call
   int subset_count = 0;
+  // virtual fields method (c8_vfm.hip)
+  double const* d_vfm_w = nullptr;   // caller's virtual field (device, kept by pointer)
+  double* d_vfm_part = nullptr;      // per-block partial sums of the VFM kernels
+  size_t vfm_part_n = 0;
 };
 
 

@@ -681,6 +681,54 @@ template <class E, template <class> class ModelT> static hipError_t launch_qoi(L
   return hipGetLastError();
 }
 
+// VFM (c8_assemble_vfm.hpp): one lane group per element as K1, KIND 0 = V, 1 = FS, 2 = A.  One wavefront per workgroup:
+// after its groups are done the block writes one partial sum per output (vfm_block_sums, fixed order) and c8_vfm.hip sums
+// the partials in a single block -- no floating-point atomics, the same bits on every run.
+constexpr int VBLOCK = 64;
+template <class E, template <class> class ModelT, int KIND>
+__global__ void __launch_bounds__(VBLOCK) k_vfm(MeshTables mt, ModelSettings ms, FieldArgs fa, VfmArgs va, SystemArgs sa, double* part,
+                                               int count, int nblocks) {
+  constexpr int GPB = VBLOCK / E::NDOF;
+  using Lane = VfmLane<E, ModelT>;
+  __shared__ GroupShared<E, ModelT<Dual>::NLOC> shs[GPB];
+  __shared__ VfmBlockSums<GPB, E::NDOF> red;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;  // the whole block
+  int const gib = threadIdx.x / E::NDOF, k = threadIdx.x % E::NDOF;
+  int const gi = lb * GPB + gib;
+  if (gib < GPB && gi < count) {
+    Lane L;
+    GpuExec<Lane> ex(k, L);
+    if constexpr (KIND == 2) vfm_adjoint_element<E, ModelT>(ex, shs[gib], mt, ms, fa, va, sa, gi);
+    else vfm_power_element<E, ModelT, KIND == 1>(ex, shs[gib], mt, ms, fa, va, sa, gi);
+    int32_t const* act = va.active + (mt.elem_set ? mt.elem_set[gi] : 0) * 10;
+    vfm_group_sums(red, gib, k, L.acc_v, L.acc_g, act[0], act[1]);
+  } else if (gib < GPB) {  // groups past the end of the mesh add nothing
+    vfm_group_sums(red, gib, k, 0., 0., 0, 0);
+  }
+  __syncthreads();
+  vfm_block_sums(red, threadIdx.x, VBLOCK, KIND != 2, KIND != 0 ? va.nact : 0, part, lb, nblocks);
+}
+template <class E, template <class> class ModelT, int KIND> static hipError_t launch_vfm(LaunchArgs const& a, VfmArgs const& va, double* part) {
+  constexpr int GPB = VBLOCK / E::NDOF;
+  if (a.count <= 0) return hipSuccess;
+  int const nblocks = (a.count + GPB - 1) / GPB;
+  int const grid = ((nblocks + 7) / 8) * 8;
+  hipLaunchKernelGGL((k_vfm<E, ModelT, KIND>), dim3(grid), dim3(VBLOCK), 0, a.stream, a.mt, a.ms, a.fa, va, a.sa, part, a.count, nblocks);
+  return hipGetLastError();
+}
+template <class E, template <class> class ModelT> struct VfmKernel {
+  static void set(KernelSet&) {}
+};
+template <template <class> class ModelT> struct VfmKernel<Tri3PlaneStress, ModelT> {
+  static void set(KernelSet& ks) {
+    ks.vfm_power = &launch_vfm<Tri3PlaneStress, ModelT, 0>;
+    ks.vfm_forward_sens = &launch_vfm<Tri3PlaneStress, ModelT, 1>;
+    ks.vfm_adjoint = &launch_vfm<Tri3PlaneStress, ModelT, 2>;
+    ks.vfm_groups_per_block = VBLOCK / Tri3PlaneStress::NDOF;
+  }
+};
+
 template <class E, template <class> class ModelT> struct WaveKernel {
   static LaunchFn get() { return nullptr; }
   static LaunchFn get_adjoint() { return nullptr; }
@@ -724,6 +772,7 @@ template <class E, template <class> class ModelT> static KernelSet kernel_set() 
   ks.stage_stride = stage_stride<E>();
   ks.adjoint_slot_stages = E::NDOF <= 16;  // the slot-per-lane adjoint kernel holds assembled columns only for small elements
   ks.can_stage = E::DIM == 3;              // the stage and the row-sum kernel are laid out for 3 + 1 equations per node
+  VfmKernel<E, ModelT>::set(ks);
   return ks;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "c8_assemble_adjoint.hpp"
+#include "c8_assemble_vfm.hpp"
 
 namespace c8 {
 
@@ -28,6 +29,8 @@ typedef hipError_t (*GatherFn)(GatherArgs const&, int first, int count, int max_
 // aa = null: forward assembly; aa != null: adjoint assembly (objective "average displacement")
 typedef hipError_t (*NodeRowsFn)(MeshTables const&, ModelSettings const&, FieldArgs const&, AdjointArgs const* aa, GatherArgs const&, int first,
                                  int count, int max_degree, int max_node_elems, hipStream_t);
+// the VFM kernels (c8_assemble_vfm.hpp): the whole mesh in one launch, one partial sum per output and block into part
+typedef hipError_t (*VfmFn)(LaunchArgs const&, VfmArgs const&, double* part);
 
 struct KernelSet {
   LaunchFn forward_jacobian;   // K1, one lane group (NDOF lanes) per element
@@ -51,6 +54,11 @@ struct KernelSet {
   int stage_stride;            // doubles per element in the stage
   bool adjoint_slot_stages;    // the slot-per-lane K3 can store into the stage (it transposes through LDS first)
   bool can_stage;              // staged (gather) assembly available for this element type
+  // virtual fields method: Tri3PlaneStress (one residual) only, else null
+  VfmFn vfm_power = nullptr;         // V
+  VfmFn vfm_forward_sens = nullptr;  // FS
+  VfmFn vfm_adjoint = nullptr;       // A
+  int vfm_groups_per_block = 0;      // element groups per block of those kernels (blocks = partial sums per output)
 };
 
 // registry keyed like the reference's string factories

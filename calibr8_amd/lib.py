@@ -136,6 +136,10 @@ SYMBOLS = [
     ("c8_solve_adjoint_local", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_param_gradient", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     ("c8_eval_qoi", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p]),
+    ("c8_vfm_set_virtual_field", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("c8_vfm_internal_power", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p]),
+    ("c8_vfm_forward_sens", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("c8_vfm_adjoint_step", C.c_int, [C.c_void_p, C.POINTER(State), C.c_double, C.c_void_p, C.c_void_p]),
     ("c8_apply_dirichlet", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Dbc), C.POINTER(C.c_void_p), C.POINTER(System), C.c_int]),
     ("c8_apply_traction", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Tbc), C.POINTER(System)]),
     ("c8_face_points", C.c_int, [C.c_int, C.c_int, dp, i32p, dp]),

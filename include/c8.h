@@ -256,6 +256,28 @@ int c8_param_gradient(c8_ctx* ctx, const c8_state* st, const double* const z[2],
 /* eval_qoi (evaluations.cpp:662-756), "average displacement" (avg_disp.cpp:16-33): *J += value. */
 int c8_eval_qoi(c8_ctx* ctx, const c8_state* st, double* J);
 
+/* ---- virtual fields method (VFM): the local constitutive update driven by MEASURED displacements, the internal-force
+ * residual contracted with a fixed nodal virtual field w; no global linear solve (virtual_power.cpp).  One-residual
+ * systems only ('mechanics_plane_stress' on tri3, virtual_power.cpp:110,148); under 'mechanics' every entry returns
+ * C8_ERR_UNSUPPORTED.  st holds the measured x (step n) and x_prev (step n-1) and the local states xi_prev, xi.
+ * Values are per part: the caller sums them over the parts, as with c8_eval_qoi and c8_param_gradient.  The sums are
+ * formed in a fixed order (no floating-point atomics): the same inputs give the same bits.  DEVICE pointers. */
+/* w [num_nodes][2], kept by pointer until the next call. */
+int c8_vfm_set_virtual_field(c8_ctx* ctx, const double* w);
+/* eval_measured_residual (evaluations.cpp:1750-1845) + VirtualPower::compute_at_step (virtual_power.cpp:135-139):
+ * the local solve from xi_prev, the converged state written to st->xi, *ivw += w^T R.  b (may be NULL) += R. */
+int c8_vfm_internal_power(c8_ctx* ctx, const c8_state* st, double* b, double* ivw);
+/* eval_measured_residual_and_grad (evaluations.cpp:1847-1973) + VirtualPower::compute_at_step_forward_sens
+ * (virtual_power.cpp:141-186): as c8_vfm_internal_power, and the local sensitivities
+ * S = -(dC/dxi)^-1 (dC/dp + dC/dxi_prev S_prev), divw[c8_num_active_params] += [(dR/dxi)^T w]^T S + (dR/dp)^T w.
+ * S, S_prev: [elems][points][local dofs][c8_num_active_params] (column = position of the parameter in grad);
+ * S_prev NULL = 0 (first step). */
+int c8_vfm_forward_sens(c8_ctx* ctx, const c8_state* st, const double* S_prev, double* S, double* ivw, double* divw);
+/* eval_vfm_adjoint_gradient (evaluations.cpp:1975-2143) at the stored state of step n, c = the step's scaled mismatch:
+ * phi = (dC/dxi)^-T (-c (dR/dxi)^T w - h), h <- (dC/dxi_prev)^T phi (in place, [elems][points][local dofs], zero
+ * before the last step), grad[c8_num_active_params] += c (dR/dp)^T w + (dC/dp)^T phi. */
+int c8_vfm_adjoint_step(c8_ctx* ctx, const c8_state* st, double c, double* h, double* grad);
+
 /* ---- next to the hot path: boundary conditions and the Newton step driver ----- */
 /* One Dirichlet condition = one entry of the deck's `dirichlet bcs` block (dbcs.cpp:59-66): residual
  * index, equation, node set, and the prescribed value at every node of the set (the caller evaluates
