@@ -207,10 +207,12 @@ template <class T, int DIM> struct SmallJ2Dim {
   // With linear hardening the return mapping has an explicit solution (radial return): from the trial stress
   // s_tr = 2 mu (dev eps - pstrain_old), dgam = (|s_tr| - sqrt(2/3)(Y + K alpha_old)) / (2 mu + 2K/3), n = s_tr / |s_tr|,
   // pstrain = pstrain_old + dgam n, alpha = alpha_old + sqrt(2/3) dgam -- the point the reference's Newton iteration
-  // (small_J2.cpp:122-173) converges to --, and the derivative of the stress through the local solve, which the
+  // (small_J2.cpp:122-173) converges to, except inside the band 0 < |f0| < abs_tol: there the iteration stops at its first
+  // test without a step, and so does this form (dgam = 0) --, and the derivative of the stress through the local solve, which the
   // reference obtains as dxi/dx = -(dC/dxi)^-1 dC/dx (evaluations.cpp:101-115), is the consistent tangent
   // ds = a dev(sym d grad u) + b n (n : dev(sym d grad u)),  a = 2 mu theta,  b = 2 mu (1 - 2 mu / H - theta),
-  // theta = 1 - 2 mu dgam / |s_tr|, H = 2 mu + 2K/3 (elastic: a = 2 mu, b = 0).  The branch is the reference's test at the
+  // theta = 1 - 2 mu dgam / |s_tr|, H = 2 mu + 2K/3 (elastic: a = 2 mu, b = 0; in the band: a = 2 mu, b = -4 mu^2 / H,
+  // the plastic equations' tangent at dgam = 0).  The branch is the reference's test at the
   // initial guess (f > tol || |f| < tol).  The forward wave kernel of hex8 uses it (c8_assemble_wave.hpp, CLOSED) in place
   // of the Newton iteration, the inverse of dC/dxi and the AD passes of phase D; every other kernel, and this one when the
   // caller asks for it (C8_KERNEL_WAVE_AD) or allows fewer than eight Newton iterations, runs the AD form above.
@@ -261,7 +263,9 @@ template <class T, int DIM> struct SmallJ2Dim {
     cf.t[2] = 0.;
     if (plastic) {
       double const inv_H = c8_rcp(2. * mu + (2. / 3.) * K);
-      double const dgam = excess * inv_H;
+      // inside the band |f0| < abs_tol the reference's iteration stops at its first test, before any step: the state stays
+      // xi_old (dgam = 0, theta = 1) and the tangent is that of the plastic equations there, b = -4 mu^2 / H
+      double const dgam = fabs(f0) < abs_tol ? 0. : excess * inv_H;
       double const inv = c8_rcp(smag);
       C8_UNROLL
       for (int k = 0; k < 9; ++k) n[k] = st[k] * inv;

@@ -292,10 +292,20 @@ def test_tiny_and_ragged_meshes():
 def test_calibration_objective(kind, wave):
     # Calibration QoI (calibration.cpp) through the kernel source on the CPU: set-up tables, preprocess (total load),
     # value, and the x / xi / parameter derivatives through K3 -> K4 -> K5, against the oracle
+    check_calibration_objective(kind, wave, "proportional")
+
+
+@pytest.mark.parametrize("kind,wave", [("hex8", True), ("hex8", "node"), ("hex8", False), ("tet4", False)])
+def test_calibration_objective_reversed_flow(kind, wave):
+    # the same at the last step of the "reverse" history: the load term of K5 at a stored state of reversed plastic flow
+    check_calibration_objective(kind, wave, "reverse")
+
+
+def check_calibration_objective(kind, wave, history):
     import numpy as np
     import oracle_lib as ol
     from parity import compare_systems, rel_vec
-    from parity_cases import J2, mesh_of, two_steps
+    from parity_cases import J2, load_history, mesh_of
     et, c, conn = mesh_of(kind)
     xmax, ymin = c[:, 0].max(), c[:, 1].min()
     loc = ([0, 1, 2], [0, 1, 3], [1, 2, 3], [0, 2, 3]) if et == ol.TET4 else \
@@ -310,8 +320,10 @@ def test_calibration_objective(kind, wave):
     dut.node = wave == "node"  # K3 in the row-per-node form: the load term's derivatives in closed form, g updated afterwards
     orc.set_calibration(faces, **kw)
     dut.set_calibration(faces, **kw)
-    st = two_steps(orc, c, 0.004)
-    (u, p, xi), (up, pp, xip) = st[2], st[1]
+    st = load_history(orc, c, 0.004, history)
+    (u, p, xi), (up, pp, xip) = st[-1], st[-2]
+    if history == "reverse":
+        assert (xi[:, :, -1] > xip[:, :, -1]).mean() > 0.3
     rng = np.random.default_rng(3)
     u_meas = u + 1e-4 * rng.standard_normal(len(u))
     for b in (orc, dut):

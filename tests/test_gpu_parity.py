@@ -605,12 +605,24 @@ def _calibration_pair(kind):
 def test_calibration_objective_matches_oracle(kind):
     # Calibration QoI (calibration.cpp): preprocess (total load), value, and its x / xi / parameter derivatives
     # through K3 -> K4 -> K5, against the oracle
-    from parity_cases import two_steps
+    check_calibration_objective(kind, "proportional")
+
+
+@pytest.mark.parametrize("kind", ["hex8", "tet4"])
+def test_calibration_objective_matches_oracle_reversed_flow(kind):
+    # the same at the last step of the "reverse" history: the load term of K5 at a stored state of reversed plastic flow
+    check_calibration_objective(kind, "reverse")
+
+
+def check_calibration_objective(kind, history):
+    from parity_cases import load_history
     orc, gpu, c = _calibration_pair(kind)
     if kind == "tet4":
         pytest.importorskip("numpy")
-    st = two_steps(orc, c, 0.004)
-    (u, p, xi), (up, pp, xip) = st[2], st[1]
+    st = load_history(orc, c, 0.004, history)
+    (u, p, xi), (up, pp, xip) = st[-1], st[-2]
+    if history == "reverse":
+        assert (xi[:, :, -1] > xip[:, :, -1]).mean() > 0.3
     rng = np.random.default_rng(3)
     u_meas = u + 1e-4 * rng.standard_normal(len(u))
     for b in (orc, gpu):

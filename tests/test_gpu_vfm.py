@@ -10,7 +10,7 @@ import pytest
 
 import oracle_lib as ol
 from parity import rel_vec
-from vfm_cases import MODELS, make_oracle, oracle_adjoint_step, oracle_power, vfm_case
+from vfm_cases import CYCLIC, MODELS, make_oracle, oracle_adjoint_step, oracle_power, vfm_case
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,9 +71,20 @@ def problem(gradient, thickness=1.0, tol=1e-8, params=TRIAL):
 @pytest.mark.parametrize("mesh", ["notch2D", "two_sets"])
 @pytest.mark.parametrize("model,params", MODELS)
 def test_vfm_kernels_match_oracle(mesh, model, params):
+    check_vfm_kernels(mesh, model, params, None)
+
+
+@pytest.mark.parametrize("mesh", ["notch2D", "two_sets"])
+@pytest.mark.parametrize("model,params", MODELS)
+def test_vfm_kernels_match_oracle_cyclic(mesh, model, params):
+    # every step of the cyclic measured sequence (hold, elastic unloading, reversed flow)
+    check_vfm_kernels(mesh, model, params, CYCLIC)
+
+
+def check_vfm_kernels(mesh, model, params, seq):
     import torch
     from calibr8_amd import Assembler
-    c, conn, es, P, active, steps, w = vfm_case(mesh, model, params)
+    c, conn, es, P, active, steps, w = vfm_case(mesh, model, params, seq)
     orc = make_oracle(c, conn, model, P, es, active)
     asm = Assembler(3, c, conn, model, P, elem_set=es)
     for s, a in enumerate(active):
@@ -86,7 +97,7 @@ def test_vfm_kernels_match_oracle(mesh, model, params):
     xi_prev = orc.new_state()
     S_prev = None
     rng = np.random.default_rng(5)
-    for n in range(1, 5):
+    for n in range(1, len(steps)):
         u, up = steps[n], steps[n - 1]
         rc, xo, bo = oracle_power(orc, u, up, xi_prev)
         assert rc == 0

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from parity import rel_vec
-from vfm_cases import MODELS, make_oracle, objective, oracle_adjoint_step, oracle_power, vfm_case
+from vfm_cases import CYCLIC, MODELS, make_oracle, objective, oracle_adjoint_step, oracle_power, vfm_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dp = C.POINTER(C.c_double)
@@ -61,7 +61,18 @@ class EmuVfm:
 @pytest.mark.parametrize("mesh", ["notch2D", "two_sets"])
 @pytest.mark.parametrize("model,params", MODELS)
 def test_vfm_kernels_match_oracle_composition(emu, mesh, model, params):
-    c, conn, es, P, active, steps, w = vfm_case(mesh, model, params)
+    check_composition(emu, mesh, model, params, None, 3)
+
+
+@pytest.mark.parametrize("mesh", ["notch2D", "two_sets"])
+@pytest.mark.parametrize("model,params", MODELS)
+def test_vfm_kernels_match_oracle_composition_cyclic(emu, mesh, model, params):
+    # every step of the cyclic measured sequence (hold, elastic unloading, reversed flow)
+    check_composition(emu, mesh, model, params, CYCLIC, len(CYCLIC))
+
+
+def check_composition(emu, mesh, model, params, seq, nsteps):
+    c, conn, es, P, active, steps, w = vfm_case(mesh, model, params, seq)
     orc = make_oracle(c, conn, model, P, es, active)
     dut = EmuVfm(emu, c, conn, model, P, es, active)
     nact = dut.nact
@@ -69,7 +80,7 @@ def test_vfm_kernels_match_oracle_composition(emu, mesh, model, params):
     xi_prev = orc.new_state()
     S_prev = None
     rng = np.random.default_rng(5)
-    for n in range(1, 3):
+    for n in range(1, nsteps):
         u, up = steps[n], steps[n - 1]
         rc, xo, bo = oracle_power(orc, u, up, xi_prev)
         assert rc == 0
@@ -131,7 +142,57 @@ def emul_objective(dut, steps, w, loads, dt_over_T, scale, thickness, P=None, gr
 
 @pytest.mark.parametrize("model,params", MODELS)
 def test_vfm_forward_and_adjoint_gradients_agree_and_match_central_differences(emu, model, params):
-    c, conn, es, P, active, steps, w = vfm_case("two_sets", model, params)
+    check_gradients(emu, model, params, None)
+
+
+@pytest.mark.parametrize("model,params", MODELS)
+def test_vfm_gradients_agree_and_match_central_differences_cyclic(emu, model, params):
+    check_gradients(emu, model, params, CYCLIC)
+
+
+@pytest.mark.parametrize("model,params", MODELS)
+def test_vfm_forward_sensitivities_match_central_differences_cyclic(emu, model, params):
+    # the local sensitivities S = dxi/dp that FS carries forward, checked directly over the cyclic sequence: against
+    # central differences of the oracle's converged state with respect to each active parameter of both sets
+    c, conn, es, P, active, steps, w = vfm_case("two_sets", model, params, CYCLIC)
+    orc = make_oracle(c, conn, model, P, es, active)
+    dut = EmuVfm(emu, c, conn, model, P, es, active)
+    nact, shape = dut.nact, (orc.nelems, orc.npts, orc.nloc)
+    Ss, xi, S_prev = [], orc.new_state(), None
+    for n in range(1, len(steps)):
+        x, S = xi.copy(), np.zeros(xi.size * nact)
+        rc, _, _ = dut.call(FS, steps[n], steps[n - 1], xi, x, w, S_prev=S_prev, S=S)
+        assert rc == 0
+        Ss.append(S.reshape(shape + (nact,)))
+        xi, S_prev = x, S
+
+    def states(Pq):
+        o = make_oracle(c, conn, model, Pq, es, active)
+        out, xp = [], o.new_state()
+        for n in range(1, len(steps)):
+            rc, xp, _ = oracle_power(o, steps[n], steps[n - 1], xp)
+            assert rc == 0
+            out.append(xp)
+        return out
+
+    k = 0
+    for s, a in enumerate(active):
+        for q in a:
+            h = 1e-5 * max(1.0, abs(P[s, q]))  # central differences: truncation ~h^2, rounding ~1e-16 |xi| / h
+            Pp, Pm = P.copy(), P.copy()
+            Pp[s, q] += h
+            Pm[s, q] -= h
+            fds = [(xp - xm) / (2 * h) for xp, xm in zip(states(Pp), states(Pm))]
+            scale = max(max(np.abs(fd).max() for fd in fds), 1e-300)  # the column's largest entry over the sequence
+            assert scale > 0
+            for n, fd in enumerate(fds):
+                err = np.abs(Ss[n][..., k] - fd).max() / scale
+                assert err <= 1e-6, (model, s, q, n + 1, err)
+            k += 1
+
+
+def check_gradients(emu, model, params, seq):
+    c, conn, es, P, active, steps, w = vfm_case("two_sets", model, params, seq)
     orc = make_oracle(c, conn, model, P, es, active)
     thickness, scale = 0.7, 1e2
     dut = EmuVfm(emu, c, conn, model, P, es, active)

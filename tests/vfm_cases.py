@@ -8,10 +8,11 @@ from parity_cases import ACTIVE, HILL_PS, HJ2_PSS, HYPO_PSS, mesh_2d
 
 MODELS = [("small_hill_plane_stress", HILL_PS), ("hyper_J2_plane_stress", HJ2_PSS), ("hypo_hill_plane_stress", HYPO_PSS)]
 STRETCH = [0.0, 1.0, 1.5, 2.0, 2.4]  # measured u_n = STRETCH[n] u_1: four steps, into the plastic range
+CYCLIC = [0.0, 1.5, 1.5, 0.8, -0.6, -1.2]  # a cyclic measured sequence: yield, hold, unloading, reversed plastic flow
 
 
-def vfm_case(mesh, model, params):
-    """(coords, conn, elem_set or None, params [sets][n], active per set, measured steps u_0..u_4, w)"""
+def vfm_case(mesh, model, params, seq=None):
+    """(coords, conn, elem_set or None, params [sets][n], active per set, measured steps u_n = seq[n] u_1 (STRETCH), w)"""
     et, c, conn = mesh_2d("notch2D" if mesh == "notch2D" else "structured")
     act = ACTIVE[model]
     if mesh == "notch2D":
@@ -22,7 +23,7 @@ def vfm_case(mesh, model, params):
         p1[2] *= 1.3
         P, active = np.vstack([params, p1]), [act[:3], act[2:5]]
     u1, _ = fields_for(2, *prescribed_fields(c, 0.004, ramp=True, perturb=5e-2))
-    steps = [s * u1 for s in STRETCH]
+    steps = [s * u1 for s in (STRETCH if seq is None else seq)]
     x, y = c[:, 0], c[:, 1]
     w = np.ascontiguousarray(np.stack([np.cos(np.pi * (y - 0.5)) * x + 0.2 * y, y * y + 0.1 * x], axis=1).ravel())
     return c, conn, es, P, active, steps, w
