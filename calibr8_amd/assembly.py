@@ -61,7 +61,7 @@ class LinearSystem:
 class Assembler:
     def __init__(self, elem_type, coords, conn, local_type, params, elem_set=None, stab_mult=1.0, max_iters=500,
                  abs_tol=1e-12, rel_tol=1e-12, device="cuda:0", scatter=None, extra_pairs=None, global_type=None,
-                 thickness=0.0, line_search=None):
+                 thickness=0.0, line_search=None, embedded=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("calibr8_amd needs a HIP device: there is no CPU execution path")
@@ -105,6 +105,11 @@ class Assembler:
         if scatter is not None:  # None: the library's default (staged assembly, see c8_set_scatter_mode)
             self.set_scatter(scatter)
         self.use_current_stream()
+        if embedded is not None:  # the `embedded model` sublist of hybrid_hyper_J2_plane_stress
+            self.set_embedded_model(embedded["activation"], embedded["topology"], embedded["input_scale"],
+                                    embedded["output_scale"])
+            if embedded.get("params") is not None:
+                self.set_embedded_params(embedded["params"])
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -154,6 +159,35 @@ class Assembler:
     def set_active(self, es, idx):
         a = np.ascontiguousarray(idx, dtype=np.int32)
         _l.check(self.L.c8_set_active_params(self.h, es, len(a), a.ctypes.data_as(_l.i32p)))
+
+    def set_embedded_model(self, activation, topology, input_scale, output_scale):
+        """Network of hybrid_hyper_J2_plane_stress: activation "relu" | "sigmoid" | "tanh" (or a C8_ACT_* value)."""
+        act = _l.C8_ACT[activation] if isinstance(activation, str) else int(activation)
+        self._topology = np.ascontiguousarray(topology, dtype=np.int32)
+        d = _l.EmbeddedModelDesc(act, len(self._topology), self._topology.ctypes.data_as(_l.i32p), float(input_scale),
+                                 float(output_scale))
+        _l.check(self.L.c8_set_embedded_model(self.h, C.byref(d)))
+
+    @property
+    def num_embedded_params(self):
+        return self.L.c8_num_embedded_params(self.h)
+
+    @property
+    def num_grad_params(self):
+        """Length of the gradient: the active parameters, then the network weights."""
+        return self.L.c8_num_grad_params(self.h)
+
+    def set_embedded_params(self, theta):
+        """Network weights in the reference's order (a `nn_params.in` file read with np.loadtxt)."""
+        t = np.ascontiguousarray(theta, dtype=np.float64).ravel()
+        if t.size != self.num_embedded_params:
+            raise ValueError("expected %d network weights, got %d" % (self.num_embedded_params, t.size))
+        _l.check(self.L.c8_set_embedded_params(self.h, t.ctypes.data_as(_l.dp)))
+
+    def get_embedded_params(self):
+        t = np.zeros(self.num_embedded_params)
+        _l.check(self.L.c8_get_embedded_params(self.h, t.ctypes.data_as(_l.dp)))
+        return t
 
     def set_scatter(self, mode):
         m = {"colored": _l.C8_SCATTER_COLORED, "atomic": _l.C8_SCATTER_ATOMIC, "gather": _l.C8_SCATTER_GATHER}[mode]

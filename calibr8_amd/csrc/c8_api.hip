@@ -48,6 +48,7 @@ static int model_id(char const* name, int ndims, int* nloc, int* nparams) {
     if (s == "small_hill_plane_stress") { *nloc = SmallHillPlaneStress<double>::NLOC; *nparams = SmallHillPlaneStress<double>::NPARAMS; return MODEL_SMALL_HILL_PLANE_STRESS; }
     if (s == "hyper_J2_plane_stress") { *nloc = HyperJ2PlaneStress<double>::NLOC; *nparams = HyperJ2PlaneStress<double>::NPARAMS; return MODEL_HYPER_J2_PLANE_STRESS; }
     if (s == "hypo_hill_plane_stress") { *nloc = HypoHillPlaneStress<double>::NLOC; *nparams = HypoHillPlaneStress<double>::NPARAMS; return MODEL_HYPO_HILL_PLANE_STRESS; }
+    if (s == "hybrid_hyper_J2_plane_stress") { *nloc = HybridHyperJ2PlaneStress<double>::NLOC; *nparams = HybridHyperJ2PlaneStress<double>::NPARAMS; return MODEL_HYBRID_HYPER_J2_PLANE_STRESS; }
     return MODEL_NONE;
   }
   if (s == "elastic") { *nloc = Elastic<double>::NLOC; *nparams = Elastic<double>::NPARAMS; return MODEL_ELASTIC; }
@@ -214,7 +215,7 @@ void c8_destroy(c8_ctx* c) {
   for (hipEvent_t e : c->ev_asm) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_sum) (void)hipEventDestroy(e);
   if (c->sum_stream) (void)hipStreamDestroy(c->sum_stream);
-  void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status};
+  void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part};
   for (void* b : bufs) (void)hipFree(b);
   delete c;
 }
@@ -246,6 +247,7 @@ int c8_init_variables(const c8_ctx* c, double* xi) {
       case MODEL_HYPO_HILL_PLANE_STRAIN: HypoHillPlaneStrain<double>::init_variables(x); break;
       case MODEL_SMALL_HILL_PLANE_STRESS: SmallHillPlaneStress<double>::init_variables(x); break;
       case MODEL_HYPER_J2_PLANE_STRESS: HyperJ2PlaneStress<double>::init_variables(x); break;
+      case MODEL_HYBRID_HYPER_J2_PLANE_STRESS: HybridHyperJ2PlaneStress<double>::init_variables(x); break;
       case MODEL_HYPO_HILL_PLANE_STRESS: HypoHillPlaneStress<double>::init_variables(x); break;
       case MODEL_HYPER_J2: HyperJ2<double>::init_variables(x); break;
       case MODEL_SMALL_HILL: SmallHill<double>::init_variables(x); break;
@@ -387,7 +389,7 @@ int c8_status(c8_ctx* c) {
 }  // extern "C"
 
 static MeshTables tables(c8_ctx const* c, bool colored) {
-  return MeshTables{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, colored ? c->d_order : nullptr, c->d_params, c->d_shape};
+  return MeshTables{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, colored ? c->d_order : nullptr, c->d_params, c->d_shape, c->d_nn};
 }
 
 // Staged (gather) assembly on the caller's stream: chunk k of the elements is assembled into the stage ring,
@@ -515,6 +517,8 @@ static int run_staged(c8_ctx* c, LaunchFn fn, FieldArgs const& fa, AdjointArgs c
 // `scatters` = the kernel adds into shared A/b entries (needs colouring or atomics).
 static int run(c8_ctx* c, LaunchFn fn, FieldArgs const& fa, AdjointArgs const& aa, SystemArgs sa, bool scatters, char const* what) {
   if (!fn) return fail(C8_ERR_UNSUPPORTED, std::string(what) + ": not available for this element/model");
+  if (c->model == MODEL_HYBRID_HYPER_J2_PLANE_STRESS && !c->nn_ready)
+    return fail(C8_ERR_ARG, std::string(what) + ": the embedded network is not set (c8_set_embedded_model, c8_set_embedded_params)");
   // staged assembly: the two Jacobian assemblies; everything else (residual-only assembly: NDOF adds per element)
   // keeps atomic adds
   bool const staged = scatters && c->scatter_mode == C8_SCATTER_GATHER && sa.A[0][0] && !c->subset &&
@@ -676,7 +680,15 @@ int c8_param_gradient(c8_ctx* c, const c8_state* st, const double* const z[2], c
   // the model's closed form (hex8 small_J2), where the caller leaves the kernel choice to the library
   if (c->ks.param_gradient_closed && c->ms.closed_form && !c->subset && (c->kernel_variant == C8_KERNEL_AUTO || c->kernel_variant == C8_KERNEL_NODE))
     fn = c->ks.param_gradient_closed;
-  return run(c, fn, field_args(st), aa, SystemArgs{}, false, "c8_param_gradient");
+  if (c->model == MODEL_HYBRID_HYPER_J2_PLANE_STRESS && c->mesh.nsets > 1)  // main_objective.cpp:259-261
+    return fail(C8_ERR_UNSUPPORTED, "c8_param_gradient: the embedded network's gradient needs a mesh with one element set");
+  int const async = c->async;
+  c->async = 1;
+  int rc = run(c, fn, field_args(st), aa, SystemArgs{}, false, "c8_param_gradient");
+  c->async = async;
+  if (rc == C8_OK) rc = c8_embedded_param_gradient(c, st, phi, grad);  // evaluations.cpp:873-879: theta after the active parameters
+  if (rc || async) return rc;
+  return c8_status(c);
 }
 
 int c8_eval_qoi(c8_ctx* c, const c8_state* st, double* J) {

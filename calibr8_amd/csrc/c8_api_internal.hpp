@@ -87,7 +87,16 @@ struct c8_ctx {
   double const* d_vfm_w = nullptr;   // caller's virtual field (device, kept by pointer)
   double* d_vfm_part = nullptr;      // per-block partial sums of the VFM kernels
   size_t vfm_part_n = 0;
+  // embedded network of hybrid_hyper_J2_plane_stress (c8_embedded.hip)
+  std::vector<double> nn_host;       // the device buffer's contents (c8_models.hpp: nn_value_slope)
+  int nn_ntheta = 0;                 // 0: no network described yet
+  bool nn_ready = false;             // the network and its weights are set
+  double* d_nn = nullptr;
+  double* d_nn_part = nullptr;       // per-block partial rows of the weight-gradient kernel
+  size_t nn_part_n = 0;
 };
+// c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
+int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);
 
 
 // c8_qoi.hip

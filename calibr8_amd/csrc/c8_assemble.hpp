@@ -44,6 +44,7 @@ struct MeshTables {
   // cached shape tables of the wave kernels (hex8), [nelems][SHAPE_STRIDE], or null: the geometry is static, so
   // dN/dx, w dv and the element size are computed once per context (store_shape_tables) instead of per call
   double const* shape = nullptr;
+  double const* nn = nullptr;  // the embedded network of hybrid_hyper_J2_plane_stress (c8_models.hpp: nn_value_slope), or null
 };
 struct ModelSettings {
   double stab_mult;
@@ -337,10 +338,15 @@ template <class E, template <class> class ModelT> struct ForwardLane {
   bool ls_done;
 };
 
+// models with an embedded network take its buffer with the parameters
+template <class Model> C8_HD void attach_embedded(Model& m, MeshTables const& mt) {
+  if constexpr (has_embedded<Model>::value) m.nn = mt.nn;
+}
 template <class Model> C8_HD void load_params(Model& m, MeshTables const& mt, int e) {
   int const es = mt.elem_set ? mt.elem_set[e] : 0;
   C8_UNROLL
   for (int q = 0; q < Model::NPARAMS; ++q) m.params[q] = Dual(mt.params[es * Model::NPARAMS + q]);
+  attach_embedded(m, mt);
 }
 
 template <class E, class EX, class SH>

@@ -93,6 +93,7 @@ C8_HD void residual_element(EX& ex, GroupShared<E, ModelT<Dual>::NLOC>& sh, Mesh
     int const es = mt.elem_set ? mt.elem_set[e] : 0;
     C8_UNROLL
     for (int q = 0; q < Model::NPARAMS; ++q) r.m.params[q] = mt.params[es * Model::NPARAMS + q];
+    attach_embedded(r.m, mt);
     if (k == 0) sh.h = elem_size<E>(sh);
   });
   ex.sync();
@@ -386,6 +387,7 @@ C8_HD void param_gradient_element(EX& ex, GroupShared<E, ModelT<Dual>::NLOC>& sh
     C8_UNROLL
     for (int q = 0; q < Model::NPARAMS; ++q)  // seed_wrt_params, local_residual.cpp:812-819
       r.m.params[q] = Dual(mt.params[es * Model::NPARAMS + q], (q == mine) ? 1. : 0.);
+    attach_embedded(r.m, mt);
     if (k == 0) sh.h = elem_size<E>(sh);
   });
   ex.sync();
@@ -457,6 +459,7 @@ C8_HD void qoi_element(EX& ex, GroupShared<E, ModelT<Dual>::NLOC>& sh, MeshTable
     int const es = mt.elem_set ? mt.elem_set[e] : 0;
     C8_UNROLL
     for (int q = 0; q < Model::NPARAMS; ++q) r.m.params[q] = mt.params[es * Model::NPARAMS + q];
+    attach_embedded(r.m, mt);
     size_t const qp = (size_t)e * E::NP0 + k;
     interpolate_values<E, double, false>(sh, k, r.g);
     C8_UNROLL

@@ -722,10 +722,12 @@ template <class E, template <class> class ModelT> struct VfmKernel {
 };
 template <template <class> class ModelT> struct VfmKernel<Tri3PlaneStress, ModelT> {
   static void set(KernelSet& ks) {
-    ks.vfm_power = &launch_vfm<Tri3PlaneStress, ModelT, 0>;
-    ks.vfm_forward_sens = &launch_vfm<Tri3PlaneStress, ModelT, 1>;
-    ks.vfm_adjoint = &launch_vfm<Tri3PlaneStress, ModelT, 2>;
-    ks.vfm_groups_per_block = VBLOCK / Tri3PlaneStress::NDOF;
+    if constexpr (!has_embedded<ModelT<Dual>>::value) {  // VFM with network weights: not available
+      ks.vfm_power = &launch_vfm<Tri3PlaneStress, ModelT, 0>;
+      ks.vfm_forward_sens = &launch_vfm<Tri3PlaneStress, ModelT, 1>;
+      ks.vfm_adjoint = &launch_vfm<Tri3PlaneStress, ModelT, 2>;
+      ks.vfm_groups_per_block = VBLOCK / Tri3PlaneStress::NDOF;
+    }
   }
 };
 
@@ -843,8 +845,34 @@ KernelSet kernels_2d(int model) {
     case MODEL_SMALL_HILL_PLANE_STRESS: return kernel_set<Tri3PlaneStress, SmallHillPlaneStress>();
     case MODEL_HYPER_J2_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HyperJ2PlaneStress>();
     case MODEL_HYPO_HILL_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HypoHillPlaneStress>();
+    case MODEL_HYBRID_HYPER_J2_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HybridHyperJ2PlaneStress>();
   }
   return KernelSet{};
+}
+
+// the weight gradient of the embedded network (c8_assemble_nn.hpp): one block per NN_GRAD_POINTS points, then one thread
+// per theta entry adds the partial rows in block order
+struct BlockExec {
+  template <class F> __device__ __forceinline__ void each(F f) { f((int)threadIdx.x); }
+  __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+__global__ void __launch_bounds__(NN_GRAD_THREADS) k_nn_param_gradient(NnGradArgs ga) {
+  __shared__ double lds[NN_LDS_SIZE];
+  BlockExec ex;
+  nn_grad_block<HybridHyperJ2PlaneStress<double>>(ex, lds, ga, blockIdx.x);
+}
+__global__ void __launch_bounds__(256) k_nn_param_gradient_reduce(double const* part, int nblocks, int ntheta, double* out) {
+  int const q = blockIdx.x * 256 + threadIdx.x;
+  if (q < ntheta) nn_grad_reduce_entry(part, nblocks, ntheta, q, out);
+}
+hipError_t launch_nn_param_gradient(NnGradArgs const& ga, double* out, hipStream_t stream) {
+  int const nblocks = nn_grad_blocks(ga.npts);
+  if (nblocks <= 0 || ga.ntheta <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nn_param_gradient, dim3(nblocks), dim3(NN_GRAD_THREADS), 0, stream, ga);
+  hipError_t const e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_nn_param_gradient_reduce, dim3((ga.ntheta + 255) / 256), dim3(256), 0, stream, ga.part, nblocks, ga.ntheta, out);
+  return hipGetLastError();
 }
 #endif
 #if C8_PART(5)
@@ -864,7 +892,8 @@ KernelSet kernels_line_search(int elem_type, int model) {
 #if C8_PART(0)
 KernelSet get_kernels(int elem_type, int model) {
   if (elem_type == C8_TRI3) return kernels_2d(model);
-  if (model >= MODEL_SMALL_HILL_PLANE_STRAIN && model <= MODEL_HYPO_HILL_PLANE_STRESS) return KernelSet{};  // the plane models exist on 2-D meshes only
+  if ((model >= MODEL_SMALL_HILL_PLANE_STRAIN && model <= MODEL_HYPO_HILL_PLANE_STRESS) || model == MODEL_HYBRID_HYPER_J2_PLANE_STRESS)
+    return KernelSet{};  // the plane models exist on 2-D meshes only
   if (elem_type != C8_HEX8 && elem_type != C8_TET4) return KernelSet{};
   if (model >= MODEL_SMALL_HOSFORD) return kernels_line_search(elem_type, model);
   if (elem_type == C8_TET4) return kernels_tet4(model);

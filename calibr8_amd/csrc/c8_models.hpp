@@ -1147,6 +1147,165 @@ template <class T> struct HyperJ2PlaneStress {
   }
 };
 
+// ---- the embedded feed-forward network of hybrid_hyper_J2_plane_stress (NN.cpp) ------------------------------------
+// Device buffer, doubles: [0] activation (C8_ACT_*), [1] number of layers n (topology entries), [2 .. 2+n) topology,
+// [NN_HEADER - 6] input scale s_in, [NN_HEADER - 5] output scale s_out, [NN_HEADER - 4] NN(0), then theta from
+// NN_HEADER on: layer by layer, W_i row-major (topology[i+1] rows, topology[i] columns), then b_i (NN.cpp get_params).
+// Input and output widths are 1; hidden widths are at most NN_MAX_WIDTH, at most NN_MAX_HIDDEN hidden layers.
+constexpr int NN_MAX_WIDTH = 64, NN_MAX_HIDDEN = 4, NN_HEADER = 16;
+constexpr int NN_ACT_RELU = 0, NN_ACT_SIGMOID = 1, NN_ACT_TANH = 2;
+C8_HD double nn_act(int act, double z) {  // relu (x > 0 ? x : 0), sigmoid, tanh
+  if (act == NN_ACT_RELU) return z > 0. ? z : 0.;
+  if (act == NN_ACT_SIGMOID) return 1. / (1. + exp(-z));
+  return tanh(z);
+}
+C8_HD double nn_act_slope(int act, double a) {  // d act / dz from the activation a = act(z)
+  if (act == NN_ACT_RELU) return a > 0. ? 1. : 0.;
+  if (act == NN_ACT_SIGMOID) return a * (1. - a);
+  return 1. - a * a;
+}
+// NN(x) and dNN/dx in plain doubles.  w: 4 * NN_MAX_WIDTH doubles (two layers of values and slopes).  The weights are
+// read at addresses that depend on the buffer and the loop counters only: wave-uniform, scalar loads on the device.
+C8_HD void nn_value_slope(double const* nn, double x, double* w, double& y, double& dy) {
+  int const act = (int)nn[0], nl = (int)nn[1];
+  double const* th = nn + NN_HEADER;
+  double *cv = w, *cd = w + NN_MAX_WIDTH, *nv = w + 2 * NN_MAX_WIDTH, *nd = w + 3 * NN_MAX_WIDTH;
+  int const n1 = (int)nn[3];
+  for (int j = 0; j < n1; ++j) {  // first hidden layer from the scalar input
+    double const a = nn_act(act, th[j] * x + th[n1 + j]);
+    cv[j] = a;
+    cd[j] = nn_act_slope(act, a) * th[j];
+  }
+  th += 2 * n1;
+  int ncur = n1;
+  for (int l = 2; l < nl - 1; ++l) {  // further hidden layers
+    int const nnext = (int)nn[2 + l];
+    double const* b = th + nnext * ncur;
+    for (int k = 0; k < nnext; ++k) {
+      double z = b[k], dz = 0.;
+      for (int j = 0; j < ncur; ++j) {
+        z += th[k * ncur + j] * cv[j];
+        dz += th[k * ncur + j] * cd[j];
+      }
+      double const a = nn_act(act, z);
+      nv[k] = a;
+      nd[k] = nn_act_slope(act, a) * dz;
+    }
+    th = b + nnext;
+    ncur = nnext;
+    double* t = cv; cv = nv; nv = t;
+    t = cd; cd = nd; nd = t;
+  }
+  double z = th[ncur], dz = 0.;  // linear output layer, width 1
+  for (int j = 0; j < ncur; ++j) {
+    z += th[j] * cv[j];
+    dz += th[j] * cd[j];
+  }
+  y = z;
+  dy = dz;
+}
+// the network's work buffer: on the device one per lane group of six lanes (the Tri3PlaneStress groups of a one-wavefront
+// block); the lanes of a group evaluate the network at the same alpha, so they write the same values
+#ifndef C8_BLOCK
+#define C8_BLOCK 64
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define C8_NN_WORK(name)                                                        \
+  __shared__ double name##_all[(C8_BLOCK + 5) / 6][4 * NN_MAX_WIDTH];          \
+  double* const name = name##_all[threadIdx.x / 6]
+#else
+#define C8_NN_WORK(name)              \
+  double name##_buf[4 * NN_MAX_WIDTH]; \
+  double* const name = name##_buf
+#endif
+// s_out (NN(s_in alpha) - NN(0)) and its derivative with respect to alpha
+C8_HD void nn_hardening(double const* nn, double alpha, double& H, double& dH) {
+  C8_NN_WORK(w);
+  double y, dy;
+  nn_value_slope(nn, nn[NN_HEADER - 6] * alpha, w, y, dy);
+  H = nn[NN_HEADER - 5] * (y - nn[NN_HEADER - 4]);
+  dH = nn[NN_HEADER - 5] * nn[NN_HEADER - 6] * dy;
+}
+C8_HD double lift_alpha(double const&, double H, double) { return H; }
+C8_HD Dual lift_alpha(Dual const& alpha, double H, double dH) { return Dual(H, dH * alpha.d); }
+
+// ---- hybrid_hyper_J2_plane_stress.cpp: hyper_J2_plane_stress with the hardening Y + s_out (NN(s_in alpha) - NN(0)) of a
+//      small feed-forward network whose weights theta are calibrated with the material parameters ("DFAD parameters",
+//      local_residual.hpp:359-378).  Local unknowns, trial state and stresses as HyperJ2PlaneStress. ------------------
+template <class T> struct HybridHyperJ2PlaneStress : HyperJ2PlaneStress<T> {
+  using Base = HyperJ2PlaneStress<T>;
+  static constexpr int NPARAMS = 3;  // E nu Y (:73-100)
+  static constexpr bool HAS_EMBEDDED = true;
+  using Trial = NoTrial;
+  double const* nn;  // the network buffer (layout above), set with the parameters (attach_embedded)
+  C8_HD Trial trial(PointState<T> const&) const { return {}; }
+  C8_HD int evaluate(PointState<T> const& g, double abs_tol, Trial const&) { return evaluate(g, abs_tol); }
+  C8_HD void initial_guess(PointState<T> const& g) {  // :246-259: zeta and Ie from the trial state, alpha = alpha_old
+    T zt[3], Ie_t, J_2D;
+    this->trial_state(g, this->xi[4], zt, Ie_t, J_2D);
+    C8_UNROLL
+    for (int k = 0; k < 3; ++k) set_val(this->xi[k], val(zt[k]));
+    set_val(this->xi[3], val(Ie_t));
+    set_val(this->xi[5], val(this->xi_prev[5]));
+  }
+  C8_HD int evaluate(PointState<T> const& g, double abs_tol, bool force_path = false, int path_in = 0) {  // :309-409
+    double const sqrt_23 = 0.81649658092772603273;
+    double const sqrt_32 = 1.22474487139158904910;
+    T* const xi = this->xi;
+    T* const R = this->R;
+    T const mu = compute_mu(this->params[0], this->params[1]), kappa = compute_kappa(this->params[0], this->params[1]);
+    T const Y = this->params[2];
+    T const Ie = xi[3], lambda_z = xi[4], alpha = xi[5], alpha_old = this->xi_prev[5];
+    T zt[3], Ie_trial, J_2D;
+    this->trial_state(g, lambda_z, zt, Ie_trial, J_2D);
+    Tens3<T> const zeta = sym_dim<2>(xi);
+    T const zeta_zz = -(xi[0] + xi[2]);
+    Tens3<T> s3 = scale(mu, zeta);  // s = mu zeta_3D
+    s3.zz = mu * zeta_zz;
+    T const s_mag = norm(s3);
+    double H, dH;
+    nn_hardening(nn, val(alpha), H, dH);
+    T const sigma_yield = Y + lift_alpha(alpha, H, dH);
+    T const f = (s_mag - sqrt_23 * sigma_yield) / val(mu);
+    T const mat_factor = kappa / (2. * mu);
+    R[4] = lambda_z - c8_sqrt((1. - zeta_zz / mat_factor) / (J_2D * J_2D));
+    int path;
+    if (!force_path) path = (val(f) > abs_tol || fabs(val(f)) < abs_tol) ? C8_PLASTIC_PATH : C8_ELASTIC_PATH;
+    else path = path_in;
+    Tens3<T> Rz = zeta - sym_dim<2>(zt);
+    if (path == C8_PLASTIC_PATH) {
+      T const dgam = sqrt_32 * (alpha - alpha_old);
+      T const c = (2. * dgam) * Ie * mu / s_mag;
+      Rz = Rz + scale(c, zeta);
+      Tens3<T> be = zeta;
+      be.xx = be.xx + Ie; be.yy = be.yy + Ie; be.zz = zeta_zz + Ie;
+      R[3] = det(be) - 1.;
+      R[5] = f;
+    } else {
+      R[3] = Ie - Ie_trial;
+      R[5] = alpha - alpha_old;
+    }
+    pack_sym_dim<2>(Rz, R);
+    return path;
+  }
+  // the weight-gradient kernel's per-point factor (c8_assemble_nn.hpp): on the unforced plastic path at the stored state,
+  // dC/dtheta = dR_alpha/dtheta = -sqrt(2/3) s_out / val(mu) (dNN(s_in alpha)/dtheta - dNN(0)/dtheta); 0 on the elastic path
+  // H = s_out (NN(s_in alpha) - NN(0)) at the stored alpha
+  C8_HD static double theta_factor(double const* prm, double H, double const* x, double abs_tol, double s_out) {
+    double const sqrt_23 = 0.81649658092772603273;
+    double const mu = compute_mu(prm[0], prm[1]);
+    Tens3<double> const zeta = sym_dim<2>(x);
+    Tens3<double> s3 = scale(mu, zeta);
+    s3.zz = mu * -(x[0] + x[2]);
+    double const s_mag = norm(s3);
+    double const f = (s_mag - sqrt_23 * (prm[2] + H)) / mu;
+    bool const plastic = f > abs_tol || fabs(f) < abs_tol;
+    return plastic ? -sqrt_23 * s_out / mu : 0.;
+  }
+};
+template <class M, class = void> struct has_embedded : std::false_type {};
+template <class M> struct has_embedded<M, std::enable_if_t<M::HAS_EMBEDDED>> : std::true_type {};
+
 // ---- hypo_hill_plane_stress.cpp: hypoelastic rate form, unrotated in-plane Cauchy stress TC (00,01,11), alpha and the
 //      out-of-plane stretch lambda_z; the material axes Q rotate the rate of deformation (:164-177) and the stress
 //      (:378-388).  The TC rows of the plastic residual are divided by val(mu) on the unforced path only (:303). ---------

@@ -57,7 +57,10 @@ class InverseProblem:
     objective and the gradient over the parts (PCU_Add_Double(J), adjoint_objective.cpp:39,99; PCU_Add_Doubles(grad),
     :109): all ranks then take the same L-BFGS steps."""
 
-    def __init__(self, make_primal, base_params, active, bounds, comm=None):
+    def __init__(self, make_primal, base_params, active, bounds, comm=None, embedded_bounds=None):
+        """embedded_bounds (hybrid_hyper_J2_plane_stress): [n_theta][2] bounds of the network weights.  The optimisation
+        vector is then [active parameters (bound-scaled), theta (unscaled, C8_SCALE_NONE)] and `make_primal(params,
+        theta)` is called (main_objective.cpp:259-263); the gradient is dJ/d[active, theta] (evaluations.cpp:873-879)."""
         self.comm = comm
         # one forward problem, or several that share the parameters (the "problems" of the reference's input,
         # objective.cpp:16-39: J and the gradient are summed over them)
@@ -68,6 +71,13 @@ class InverseProblem:
         b = np.asarray(bounds, dtype=np.float64)
         self.lo, self.hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
         self.kind = np.full(len(self.active), _l.C8_SCALE_BOUNDS, dtype=np.int32)
+        self.n_theta = 0
+        if embedded_bounds is not None:
+            eb = np.asarray(embedded_bounds, dtype=np.float64)
+            self.n_theta = eb.shape[0]
+            self.lo = np.ascontiguousarray(np.concatenate([self.lo, eb[:, 0]]))
+            self.hi = np.ascontiguousarray(np.concatenate([self.hi, eb[:, 1]]))
+            self.kind = np.concatenate([self.kind, np.full(self.n_theta, _l.C8_SCALE_NONE, dtype=np.int32)])
         self.history = []
 
     def _tr(self, v, from_canonical):
@@ -89,12 +99,14 @@ class InverseProblem:
         from .primal import adjoint_gradient
         L = _l.load_library()
         phys = self.to_physical(canonical)
+        na = len(self.active)
         params = self.base.copy()
-        params[self.active] = phys
-        J, g = 0.0, np.zeros(len(self.active))
+        params[self.active] = phys[:na]
+        theta = phys[na:]
+        J, g = 0.0, np.zeros(len(phys))
         for make in self.problems:
             try:
-                pr = make(params)
+                pr = make(params, theta) if self.n_theta else make(params)
             except (RuntimeError, _l.C8Error):
                 pr = None  # the forward problem failed at these parameters (adjoint_objective.cpp lets ROL back off)
             if self.comm is not None:  # every part backs off together
@@ -104,7 +116,7 @@ class InverseProblem:
                 return None
             pr.asm.set_active(0, self.active)
             J += pr.qoi()
-            g += np.ascontiguousarray(adjoint_gradient(pr, len(self.active)))
+            g += np.ascontiguousarray(adjoint_gradient(pr, len(phys)))
             del pr
         if self.comm is not None:
             red = self.comm.allreduce(np.concatenate([[J], g]))
@@ -117,9 +129,17 @@ class InverseProblem:
         self.history.append((phys.copy(), float(J)))
         return J, gc
 
-    def solve(self, initial_active, **opts):
-        x0 = self.to_canonical(initial_active)
-        x, info = lbfgs_minimize(self.value_and_gradient, x0, -1.0, 1.0, **opts)
+    def solve(self, initial_active, initial_theta=None, **opts):
+        """With embedded_bounds: returns [active, theta] and starts from initial_theta."""
+        if not self.n_theta:
+            x0 = self.to_canonical(initial_active)
+            x, info = lbfgs_minimize(self.value_and_gradient, x0, -1.0, 1.0, **opts)
+            return self.to_physical(x), info
+        x0 = self.to_canonical(np.concatenate([np.asarray(initial_active, dtype=np.float64), np.asarray(initial_theta, dtype=np.float64)]))
+        na = len(self.active)
+        lo = np.concatenate([np.full(na, -1.0), self.lo[na:]])
+        hi = np.concatenate([np.full(na, 1.0), self.hi[na:]])
+        x, info = lbfgs_minimize(self.value_and_gradient, x0, lo, hi, **opts)
         return self.to_physical(x), info
 
 

@@ -84,6 +84,14 @@ ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
+C8_ACT = {"relu": 0, "sigmoid": 1, "tanh": 2}  # C8_ACT_* of c8.h, by the deck's "activation function" names
+
+
+class EmbeddedModelDesc(C.Structure):
+    _fields_ = [("activation", C.c_int32), ("num_layers", C.c_int32), ("topology", C.POINTER(C.c_int32)),
+                ("input_scale", C.c_double), ("output_scale", C.c_double)]
+
+
 class State(C.Structure):
     _fields_ = [("x", C.c_void_p * 2), ("x_prev", C.c_void_p * 2), ("xi_prev", C.c_void_p), ("xi", C.c_void_p)]
 
@@ -111,6 +119,11 @@ SYMBOLS = [
     ("c8_set_params", C.c_int, [C.c_void_p, dp]),
     ("c8_set_active_params", C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p]),
     ("c8_num_active_params", C.c_int, [C.c_void_p]),
+    ("c8_set_embedded_model", C.c_int, [C.c_void_p, C.POINTER(EmbeddedModelDesc)]),
+    ("c8_num_embedded_params", C.c_int, [C.c_void_p]),
+    ("c8_set_embedded_params", C.c_int, [C.c_void_p, dp]),
+    ("c8_get_embedded_params", C.c_int, [C.c_void_p, dp]),
+    ("c8_num_grad_params", C.c_int, [C.c_void_p]),
     ("c8_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("c8_set_scatter_mode", C.c_int, [C.c_void_p, C.c_int]),
     ("c8_get_scatter_mode", C.c_int, [C.c_void_p]),

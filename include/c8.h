@@ -75,7 +75,8 @@ typedef struct {
                                        "hypo_hill" | "small_hosford" | "hypo_hosford" | "hypo_barlat"; on tri3 meshes "small_J2" | "small_hill_plane_strain" |
                                        "hyper_J2_plane_strain" | "hypo_hill_plane_strain", and under
                                        mechanics_plane_stress "small_hill_plane_stress" | "hyper_J2_plane_stress" |
-                                       "hypo_hill_plane_stress" (the names of local_residual.cpp:893-933) */
+                                       "hypo_hill_plane_stress" | "hybrid_hyper_J2_plane_stress" (the names of
+                                       local_residual.cpp:893-933; the hybrid model needs c8_set_embedded_model) */
   double stabilization_multiplier;  /* mechanics.cpp:47 */
   int32_t local_max_iters;          /* "nonlinear max iters" of the local residual */
   double local_abs_tol;             /* "nonlinear absolute tol" */
@@ -87,7 +88,8 @@ typedef struct {
                                        and dp_01 .. dp_55), small_hill_plane_strain /
                                        hypo_hill_plane_strain 9 (E nu Y S D R00 R11 R22 R01), hyper_J2_plane_strain 6 (E nu K Y Y_inf delta),
                                        small_hill_plane_stress 9 (as plane strain), hyper_J2_plane_stress 8 (as hyper_J2),
-                                       hypo_hill_plane_stress 13 (the nine + Q00 Q01 Q10 Q11) */
+                                       hypo_hill_plane_stress 13 (the nine + Q00 Q01 Q10 Q11),
+                                       hybrid_hyper_J2_plane_stress 3 (E nu Y) */
   const double* params;             /* [num_elem_sets][num_params] */
   double thickness;                 /* mechanics_plane_stress.cpp:22 "thickness"; 0 = the reference's default 1 */
   /* `line search:` sublist of the local residual (line_search.hpp:40-49), used by the local Newton iteration of
@@ -143,6 +145,32 @@ int c8_set_params(c8_ctx* ctx, const double* params_host); /* LocalResidual::set
  * (small_J2.cpp:96-98 default = {0}; objective.cpp:110-115 overrides from the inverse block). */
 int c8_set_active_params(c8_ctx* ctx, int elem_set, int n, const int32_t* param_idx);
 int c8_num_active_params(const c8_ctx* ctx); /* total over element sets = length of grad */
+
+/* ---- embedded network of "hybrid_hyper_J2_plane_stress" (hybrid_hyper_J2_plane_stress.cpp, NN.cpp) ----------------
+ * The hardening is sigma_y = Y + output_scale (NN(input_scale alpha) - NN(0)) with a feed-forward network NN: hidden
+ * layers x_{i+1} = act(W_i x_i + b_i), a linear last layer.  The entries map to the deck's `embedded model` sublist:
+ *   activation    "activation function": "relu" -> C8_ACT_RELU, "sigmoid" -> C8_ACT_SIGMOID, "tanh" -> C8_ACT_TANH
+ *   topology      "topology" (num_layers entries, at least 3; input and output width 1, at most 4 hidden layers of at
+ *                 most 64 units; HOST array, copied)
+ *   input_scale   "input scale";  output_scale  "output scale"
+ *   theta         "read parameters": the file nn_params.in, one value per line, in the order of c8_set_embedded_params
+ * NN(0) is evaluated on the device by the code that evaluates NN(input_scale alpha), so the hardening is exactly Y at
+ * alpha = 0.  The weights theta are the reference's DFAD parameters: layer by layer W_i row-major (topology[i+1] rows,
+ * topology[i] columns), then b_i.  c8_param_gradient and c8_adjoint_solve_step append their gradient to grad:
+ * grad[c8_num_active_params .. + c8_num_embedded_params) (evaluations.cpp:873-879); that needs a mesh with one element
+ * set (main_objective.cpp:259-261, else C8_ERR_UNSUPPORTED).  Assemblies of a hybrid context return C8_ERR_ARG until
+ * the network and theta are set.  The c8_vfm_* entry points do not support the hybrid model. */
+enum { C8_ACT_RELU = 0, C8_ACT_SIGMOID = 1, C8_ACT_TANH = 2 };
+typedef struct {
+  int32_t activation, num_layers;
+  const int32_t* topology;  /* HOST, copied */
+  double input_scale, output_scale;
+} c8_embedded_model_desc;
+int c8_set_embedded_model(c8_ctx* ctx, const c8_embedded_model_desc* desc); /* C8_ERR_UNSUPPORTED for other models */
+int c8_num_embedded_params(const c8_ctx* ctx);                               /* 0 for other models */
+int c8_set_embedded_params(c8_ctx* ctx, const double* theta_host);
+int c8_get_embedded_params(const c8_ctx* ctx, double* theta_host);
+int c8_num_grad_params(const c8_ctx* ctx); /* c8_num_active_params + c8_num_embedded_params = length of grad */
 int c8_set_stream(c8_ctx* ctx, void* hip_stream);
 int c8_set_scatter_mode(c8_ctx* ctx, int mode); /* C8_SCATTER_GATHER (default, see above), C8_SCATTER_ATOMIC or C8_SCATTER_COLORED */
 int c8_get_scatter_mode(const c8_ctx* ctx);
