@@ -110,12 +110,24 @@ template <class EX> C8_HD void nn_chunk_backward(EX& ex, double* lds, double con
       }
     });
     if (l == 0) break;
-    ex.each([&](int t) {  // deltas of hidden layer l (width n0) into dnext
+    // deltas of hidden layer l (width n0) into dnext.  The slope is formed from the pre-activation z, recomputed here as the
+    // forward pass formed it from the layer below (LDS keeps the activations only)
+    int const nb = (int)nn[1 + l];  // width of the layer below hidden layer l
+    double const* Wb = th + toff[l - 1];
+    ex.each([&](int t) {
       for (int i = t; i < NN_GRAD_CHUNK * n0; i += NN_GRAD_THREADS) {
         int const p = i / n0, k = i - p * n0;
         double s = 0.;
         for (int j = 0; j < n1; ++j) s += W[j * n0 + k] * delta(p, j);
-        lds[dnext + p * n0 + k] = nn_act_slope(act, lds[aoff[l] + p * n0 + k]) * s;
+        double z;
+        if (l == 1) {
+          z = Wb[k] * lds[NN_LDS_X + p] + Wb[n0 + k];
+        } else {
+          double const* a = lds + aoff[l - 1] + p * nb;
+          z = Wb[n0 * nb + k];
+          for (int q = 0; q < nb; ++q) z += Wb[k * nb + q] * a[q];
+        }
+        lds[dnext + p * n0 + k] = nn_act_slope(act, z) * s;
       }
     });
     ex.sync();

@@ -1159,10 +1159,17 @@ C8_HD double nn_act(int act, double z) {  // relu (x > 0 ? x : 0), sigmoid, tanh
   if (act == NN_ACT_SIGMOID) return 1. / (1. + exp(-z));
   return tanh(z);
 }
-C8_HD double nn_act_slope(int act, double a) {  // d act / dz from the activation a = act(z)
-  if (act == NN_ACT_RELU) return a > 0. ? 1. : 0.;
-  if (act == NN_ACT_SIGMOID) return a * (1. - a);
-  return 1. - a * a;
+// d act / dz at the pre-activation z, as the reference's Sacado rules form it: 0 at the relu kink, the quotient rule
+// e / (1 + e)^2 of 1 / (1 + e), e = exp(-z), taken at -|z| (the same value, no overflow), and 1 / cosh^2(z).  Formed from z,
+// not from a = act(z): 1 - a^2 and a (1 - a) keep only the digits of a saturated a (|z| = 8: 1e-9 relative)
+C8_HD double nn_act_slope(int act, double z) {
+  if (act == NN_ACT_RELU) return z > 0. ? 1. : 0.;
+  if (act == NN_ACT_SIGMOID) {
+    double const e = exp(-fabs(z)), d = 1. + e;
+    return e / (d * d);
+  }
+  double const c = cosh(z);
+  return 1. / (c * c);
 }
 // NN(x) and dNN/dx in plain doubles.  w: 4 * NN_MAX_WIDTH doubles (two layers of values and slopes).  The weights are
 // read at addresses that depend on the buffer and the loop counters only: wave-uniform, scalar loads on the device.
@@ -1172,9 +1179,9 @@ C8_HD void nn_value_slope(double const* nn, double x, double* w, double& y, doub
   double *cv = w, *cd = w + NN_MAX_WIDTH, *nv = w + 2 * NN_MAX_WIDTH, *nd = w + 3 * NN_MAX_WIDTH;
   int const n1 = (int)nn[3];
   for (int j = 0; j < n1; ++j) {  // first hidden layer from the scalar input
-    double const a = nn_act(act, th[j] * x + th[n1 + j]);
-    cv[j] = a;
-    cd[j] = nn_act_slope(act, a) * th[j];
+    double const z = th[j] * x + th[n1 + j];
+    cv[j] = nn_act(act, z);
+    cd[j] = nn_act_slope(act, z) * th[j];
   }
   th += 2 * n1;
   int ncur = n1;
@@ -1187,9 +1194,8 @@ C8_HD void nn_value_slope(double const* nn, double x, double* w, double& y, doub
         z += th[k * ncur + j] * cv[j];
         dz += th[k * ncur + j] * cd[j];
       }
-      double const a = nn_act(act, z);
-      nv[k] = a;
-      nd[k] = nn_act_slope(act, a) * dz;
+      nv[k] = nn_act(act, z);
+      nd[k] = nn_act_slope(act, z) * dz;
     }
     th = b + nnext;
     ncur = nnext;

@@ -186,6 +186,12 @@ inline Fad acos(Fad const& a) {
   for (int i = 0; i < a.n; ++i) r.d[i] = s * a.d[i];
   return r;
 }
+inline Fad tanh(Fad const& a) {  // Sacado's TanhOp: dx / cosh^2(x)
+  Fad r; r.v = std::tanh(a.v); r.n = a.n;
+  double const c = std::cosh(a.v);
+  for (int i = 0; i < a.n; ++i) r.d[i] = a.d[i] / (c * c);
+  return r;
+}
 inline Fad abs(Fad const& a) {
   Fad r; r.v = std::fabs(a.v); r.n = a.n;
   double const s = a.v >= 0. ? 1. : -1.;
@@ -210,6 +216,7 @@ using std::cbrt;
 using std::exp;
 using std::pow;
 using std::sqrt;
+using std::tanh;
 
 // ---------------------------------------------------------------------------
 // Tensor algebra (the MiniTensor subset the hot models use, a15 of SURVEY.md section 8a):
@@ -1987,6 +1994,113 @@ template <class T> struct HyperJ2PlaneStress : Local<T> {
 };
 
 
+// hybrid_hyper_J2_plane_stress.cpp: HyperJ2PlaneStress with params E nu Y, then the weights theta of a feed-forward network
+// (NN.cpp: hidden layers act(W x + b), a linear last layer; theta = W_0, b_0, W_1, b_1, ... with W_l row-major, the order
+// of FFNN::get_params).  The hardening is Y + s_out (NN(s_in alpha) - NN(0)) (nn_hardening).  The network is evaluated in
+// T, so Fad carries dNN/dalpha when xi is seeded and dNN/dtheta when theta is (seed_wrt_params): K5 with theta indices
+// active is the reference's DFAD weight gradient.  Activation ids: 0 relu, 1 sigmoid, 2 tanh.
+template <class T> static T nn_activation(int act, T const& x) {  // NN.cpp relu, sigmoid, my_tanh
+  if (act == 0) return x > 0. ? x : T(0.);
+  if (act == 1) return 1. / (1. + exp(-x));
+  return tanh(x);
+}
+template <class T> struct HybridHyperJ2PlaneStress : HyperJ2PlaneStress<T> {
+  int act = 2;
+  std::vector<int> topology;  // [1, hidden widths..., 1]
+  double s_in = 1., s_out = 1.;
+  int num_theta() const {
+    int n = 0;
+    for (size_t l = 0; l + 1 < topology.size(); ++l) n += topology[l + 1] * (topology[l] + 1);
+    return n;
+  }
+  int num_params() const override { return 3 + num_theta(); }
+  T nn(T const& x) const {  // FFNN::evaluate, theta from params[3]
+    std::vector<T> h(1, x), z;
+    int o = 3;
+    int const L = (int)topology.size() - 1;
+    for (int l = 0; l < L; ++l) {
+      int const n0 = topology[l], n1 = topology[l + 1];
+      z.assign(n1, T(0.));
+      for (int j = 0; j < n1; ++j) {
+        T s = this->params[o + j * n0] * h[0];
+        for (int k = 1; k < n0; ++k) s += this->params[o + j * n0 + k] * h[k];
+        s += this->params[o + n1 * n0 + j];
+        z[j] = (l < L - 1) ? nn_activation(act, s) : s;
+      }
+      o += n1 * (n0 + 1);
+      h.swap(z);
+    }
+    return h[0];
+  }
+  T hardening(T const& alpha) const { return s_out * (nn(s_in * alpha) - nn(0. * alpha)); }  // nn_hardening
+  int solve_nonlinear(Global<T>& g) override {  // zeta and Ie from the trial state, alpha = alpha_old; plain Newton
+    if (std::is_same<T, double>::value) return 0;
+    {
+      T J_2D;
+      Tens<T> bt;
+      this->be_bar_trial(g, this->sym_tensor_xi_prev(0), this->scalar_xi_prev(1), this->scalar_xi_prev(2), this->scalar_xi(2), J_2D, bt);
+      T const Ie_trial = (bt(0, 0) + bt(1, 1) + bt(2, 2)) / 3.;
+      Tens<T> const zeta_trial_3D = bt - Ie_trial * eye<T>(3);
+      this->set_sym_tensor_xi_val(0, this->in_plane(zeta_trial_3D));
+      this->set_scalar_xi_val(1, val(Ie_trial));
+      this->set_scalar_xi_val(3, val(this->scalar_xi_prev(3)));
+    }
+    return this->newton(g);
+  }
+  int evaluate(Global<T>& g, bool force_path, int path_in) override {  // hyper_J2_plane_stress's, with the network hardening
+    int path = ELASTIC_PATH;
+    double const sqrt_23 = std::sqrt(2. / 3.), sqrt_32 = std::sqrt(3. / 2.);
+    T const E = this->params[0], nu = this->params[1], Y = this->params[2];
+    T const mu = compute_mu(E, nu), kappa = compute_kappa(E, nu);
+    Tens<T> const zeta_old = this->sym_tensor_xi_prev(0);
+    T const Ie_old = this->scalar_xi_prev(1), lambda_z_old = this->scalar_xi_prev(2), alpha_old = this->scalar_xi_prev(3);
+    Tens<T> const zeta = this->sym_tensor_xi(0);
+    T const Ie = this->scalar_xi(1), lambda_z = this->scalar_xi(2), alpha = this->scalar_xi(3);
+    Tens<T> const I = eye<T>(3);
+    T J_2D;
+    Tens<T> bt;
+    this->be_bar_trial(g, zeta_old, Ie_old, lambda_z_old, lambda_z, J_2D, bt);
+    T const Ie_trial = (bt(0, 0) + bt(1, 1) + bt(2, 2)) / 3.;
+    Tens<T> const zeta_trial_2D = this->in_plane(bt - Ie_trial * I);
+    Tens<T> zeta_3D = into_3d(zeta);
+    T const zeta_zz = -(zeta(0, 0) + zeta(1, 1));
+    zeta_3D(2, 2) = zeta_zz;
+    Tens<T> const be_bar = zeta_3D + Ie * I;
+    Tens<T> const s = mu * zeta_3D;
+    T const s_mag = norm(s);
+    T const sigma_yield = Y + hardening(alpha);
+    T const f = (s_mag - sqrt_23 * sigma_yield) / val(mu);
+    T const mat_factor = kappa / (2. * mu);
+    T const R_lambda_z = lambda_z - sqrt((1. - zeta_zz / mat_factor) / (J_2D * J_2D));
+    bool plastic;
+    if (!force_path) {
+      plastic = (f > this->abs_tol || abs(val(f)) < this->abs_tol);
+      path = plastic ? PLASTIC_PATH : ELASTIC_PATH;
+    } else {
+      path = path_in;
+      plastic = (path == PLASTIC_PATH);
+    }
+    Tens<T> R_zeta;
+    T R_Ie, R_alpha;
+    if (plastic) {
+      Tens<T> const n_2D = mu * zeta / s_mag;
+      T const dgam = sqrt_32 * (alpha - alpha_old);
+      R_zeta = zeta - zeta_trial_2D + 2. * dgam * Ie * n_2D;
+      R_Ie = det(be_bar) - 1.;
+      R_alpha = f;
+    } else {
+      R_zeta = zeta - zeta_trial_2D;
+      R_Ie = Ie - Ie_trial;
+      R_alpha = alpha - alpha_old;
+    }
+    this->set_sym_tensor_R(0, R_zeta);
+    this->set_scalar_R(1, R_Ie);
+    this->set_scalar_R(2, R_lambda_z);
+    this->set_scalar_R(3, R_alpha);
+    return path;
+  }
+};
+
 // hypo_hill_plane_stress.cpp (TC SYM_TENSOR (00,01,11), alpha, lambda_z SCALAR; params E nu Y S D R00 R11 R22 R01 Q00 Q01
 // Q10 Q11): the material axes Q enter the rate of deformation (:164-177) and the rotated stress (:378-388); the TC rows of
 // the plastic residual are divided by val(mu) on the unforced path only (:303), as the reference does.
@@ -2503,6 +2617,7 @@ template <class T> Local<T>* make_local(std::string const& type, int ndims = 3) 
     if (type == "hypo_hill_plane_strain") return new HypoHillPlaneStrain<T>();
     if (type == "small_hill_plane_stress") return new SmallHillPlaneStress<T>();  // these three pair with mechanics_plane_stress
     if (type == "hyper_J2_plane_stress") return new HyperJ2PlaneStress<T>();
+    if (type == "hybrid_hyper_J2_plane_stress") return new HybridHyperJ2PlaneStress<T>();
     if (type == "hypo_hill_plane_stress") return new HypoHillPlaneStress<T>();
     return nullptr;
   }
@@ -3231,6 +3346,28 @@ int c8o_npts(void* h) { return ((Ctx*)h)->ngpts; }
 void c8o_set_params(void* h, double const* params) {
   Ctx* c = (Ctx*)h;
   c->params.assign(params, params + (size_t)c->nsets * c->nparams);
+}
+// the `embedded model:` sublist of hybrid_hyper_J2_plane_stress (activation 0 relu, 1 sigmoid, 2 tanh; topology; input and
+// output scales).  The parameters become E nu Y theta: the first three of every set are kept, theta is zero until
+// c8o_set_params.  Returns the number of parameters, or -1 for another model or a topology without hidden layers.
+int c8o_set_embedded(void* h, int act, int nlayers, int const* topology, double s_in, double s_out) {
+  Ctx* c = (Ctx*)h;
+  auto* ld = dynamic_cast<HybridHyperJ2PlaneStress<double>*>(c->local_d);
+  auto* lf = dynamic_cast<HybridHyperJ2PlaneStress<Fad>*>(c->local_f);
+  if (!ld || !lf || nlayers < 3 || topology[0] != 1 || topology[nlayers - 1] != 1 || act < 0 || act > 2) return -1;
+  for (int l = 0; l < nlayers; ++l) if (topology[l] < 1) return -1;
+  ld->act = lf->act = act;
+  ld->topology.assign(topology, topology + nlayers);
+  lf->topology = ld->topology;
+  ld->s_in = lf->s_in = s_in;
+  ld->s_out = lf->s_out = s_out;
+  int const np = ld->num_params();
+  std::vector<double> p((size_t)c->nsets * np, 0.);
+  for (int es = 0; es < c->nsets; ++es)
+    for (int k = 0; k < 3; ++k) p[(size_t)es * np + k] = c->params[(size_t)es * c->nparams + k];
+  c->nparams = np;
+  c->params = p;
+  return np;
 }
 // Calibration QoI (calibration.cpp:13-50 parameters; :55-160 before_elems).  faces: [nfaces][npf] global node ids
 // of the displacement side set; load plane: nodes with |x[coord_idx] - coord_value| < coord_tol (qoi.cpp:160-198).

@@ -46,6 +46,8 @@ def lib():
         L.c8o_set_local_line_search.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
         L.c8o_npts.argtypes = [C.c_void_p]
         L.c8o_set_params.argtypes = [C.c_void_p, dp]
+        L.c8o_set_embedded.restype = C.c_int
+        L.c8o_set_embedded.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, C.c_double]
         L.c8o_set_active.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
         L.c8o_init_variables.argtypes = [C.c_void_p, dp]
         L.c8o_graph_nnz.restype = C.c_int64
@@ -101,7 +103,9 @@ class LinSys:
 
 class Oracle:
     def __init__(self, elem_type, coords, conn, local_type, params, elem_set=None, stab_mult=1.0,
-                 max_iters=500, abs_tol=1e-12, rel_tol=1e-12, extra_pairs=None):
+                 max_iters=500, abs_tol=1e-12, rel_tol=1e-12, extra_pairs=None, embedded=None):
+        """embedded (hybrid_hyper_J2_plane_stress): dict(activation, topology, input_scale, output_scale, params), the
+        `embedded model:` sublist with the weights theta; the model's parameters are then E nu Y theta"""
         L = lib()
         self.L = L
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
@@ -141,6 +145,11 @@ class Oracle:
                 ci = np.zeros(self.nnz[i][j], dtype=np.int32)
                 L.c8o_graph(self.h, i, j, rp.ctypes.data_as(C.POINTER(C.c_int64)), _i(ci))
                 self.rowptr[i][j], self.colidx[i][j] = rp, ci
+        if embedded is not None:
+            self.set_embedded(embedded["activation"], embedded["topology"], embedded["input_scale"],
+                              embedded["output_scale"])
+            theta = np.asarray(embedded["params"], dtype=np.float64)
+            self.set_params([list(row[:3]) + list(theta) for row in self.params])
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -157,6 +166,19 @@ class Oracle:
     def set_params(self, params):
         self.params = np.ascontiguousarray(np.atleast_2d(np.asarray(params, dtype=np.float64)))
         self.L.c8o_set_params(self.h, _d(self.params))
+
+    ACTIVATIONS = {"relu": 0, "sigmoid": 1, "tanh": 2}
+
+    def set_embedded(self, activation, topology, input_scale, output_scale):
+        """hybrid_hyper_J2_plane_stress: the network (theta becomes zero; set it with set_params)"""
+        t = np.ascontiguousarray(topology, dtype=np.int32)
+        n = self.L.c8o_set_embedded(self.h, self.ACTIVATIONS[activation], len(t), _i(t), float(input_scale),
+                                    float(output_scale))
+        if n < 0:
+            raise ValueError("c8o_set_embedded refused %s %r" % (activation, list(topology)))
+        prm = np.zeros((self.nsets, n))
+        prm[:, :3] = self.params[:, :3]
+        self.params = prm
 
     def set_active(self, es, idx):
         a = np.ascontiguousarray(idx, dtype=np.int32)

@@ -328,7 +328,9 @@ def check_residual(orc, dut, c, eps, tol, history="proportional"):
         assert rel_vec(ls_d.b[0], ls_j.b[0]) < 1e-10 and rel_vec(ls_d.b[1], ls_j.b[1]) < 1e-10
 
 
-def check_adjoint_chain(orc, dut, c, model, eps, tol, history="proportional"):
+def check_adjoint_chain(orc, dut, c, model, eps, tol, history="proportional", k5_hook=None):
+    """K3-K6 backwards over the steps of a history; k5_hook(n, step, z_u, z_p, phi), if given, is called after K5 of step n
+    with step = (u, p, u_prev, p_prev, xi_prev, xi) and the oracle's local adjoint phi (further gradient checks)"""
     st = load_history(orc, c, eps, history)
     act = ACTIVE[model]
     orc.set_active(0, act)
@@ -394,6 +396,8 @@ def check_adjoint_chain(orc, dut, c, model, eps, tol, history="proportional"):
             assert not bad, ("qoi_gradient", n, bad, gr_d, gr_o, gr_scale, sens)
             AUDIT.fire(model, "ulp_sens", ("qoi_gradient", n, k5.max()))
         assert k5.max() < tol or history != "proportional", ("qoi_gradient", n, gr_d, gr_o, gr_scale)
+        if k5_hook is not None:
+            k5_hook(n, (u, p, up, pp, xip, xi), z_u, z_p, phi_o)
         # K6
         assert abs(dut.eval_qoi(u, p) - orc.eval_qoi(u, p)) < tol * max(1.0, abs(orc.eval_qoi(u, p)))
 

@@ -13,13 +13,13 @@ import emul_lib as el
 import hybrid_ref as hr
 import oracle_lib as ol
 import parity_cases as pc
-from hybrid_cases import ABS_TOL, E, NU, Y, dK_dtheta, linear_relu_net, stretch, tri_mesh
+from hybrid_cases import (ABS_TOL, E, HYB, NETS, NU, Y, assert_allowances, check_purpose, dK_dtheta, hybrid_oracle,
+                          linear_relu_net, oracle_theta_gradient, stretch, theta_sample, tri_mesh)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int)
 REL_TOL = 1e-12
-HYB = "hybrid_hyper_J2_plane_stress"
 pc.ACTIVE.setdefault(HYB, [0, 1, 2])  # E nu Y: the same indices in the hybrid model and in hyper_J2_plane_stress
 
 
@@ -256,3 +256,79 @@ def test_converged_state_satisfies_the_restated_hardening(emu, act, topo):
         assert np.all(f[~moved] < 1e-10)
         xip, up = xi, u
     assert nplastic > 0
+
+
+# ---- the network catalogue (hybrid_cases.NETS) against the oracle's hybrid class ------------------------------------------
+def emul_theta_gradient(emu, net, xi, phi, npts=None):
+    """c8emu_nn_grad over the first npts points of xi / phi ([..., 6]): the weight-gradient kernel, block after block"""
+    xi = np.ascontiguousarray(np.asarray(xi).reshape(-1, 6))
+    phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 6))
+    npts = len(xi) if npts is None else npts
+    buf = net.buffer()
+    P = np.ascontiguousarray([E, NU, Y])
+    got = np.zeros(len(net.theta))
+    assert emu.c8emu_nn_grad(npts, 1, 6, 3, ABS_TOL, buf.ctypes.data_as(dp), xi.ctypes.data_as(dp),
+                             phi.ctypes.data_as(dp), None, P.ctypes.data_as(dp), len(got), got.ctypes.data_as(dp)) == 0
+    return got
+
+
+# every catalogue network on both meshes and all five histories; the widest on the structured mesh with two histories
+# (the oracle evaluates its 12673 weights in forward-mode AD, ~40 s per history there)
+CATALOGUE_RUNS = [(n, k, h) for n in sorted(NETS) if n != "tanh_widest" for k in ("structured", "notch2D")
+                  for h in pc.HISTORIES] + [("tanh_widest", "structured", h) for h in ("proportional", "reverse")]
+
+
+@pytest.mark.parametrize("name,kind,history", CATALOGUE_RUNS)
+def test_catalogue_k1_to_k5_and_weight_gradient_against_oracle(emu, name, kind, history):
+    # K1 (forward), K2 (residual), K3-K6 (adjoint chain, K5 along E nu Y) of the hybrid kernels against the oracle's hybrid
+    # class, every step, at 1e-12 with no allowance; at every step of the chain the weight-gradient kernel with the chain's
+    # phi against the oracle's K5 along theta
+    net = NETS[name]
+    orc, c, conn = hybrid_oracle(kind, net)
+    et = pc.mesh_2d(kind)[0]
+    dut = HybridEmul(emu, c, conn, net.buffer(), et)
+    used = dict(pc.AUDIT.used)
+    pc.check_forward(orc, dut, c, HYB, 0.004, 1e-12, history)
+    pc.check_residual(orc, dut, c, 0.004, 1e-12, history)
+    idx = theta_sample(net) if name == "tanh_widest" else None
+    seen = []
+
+    def theta_check(n, step, z_u, z_p, phi):
+        want, scale = oracle_theta_gradient(orc, step, z_u, z_p, phi, idx)
+        got = emul_theta_gradient(emu, net, step[5], phi)
+        got = got if idx is None else got[idx]
+        # the bar of the linear-network test: 1e-12 of the largest sum of product magnitudes (the kernel adds the NN(0)
+        # term once per block, the oracle once per point)
+        assert np.max(np.abs(got - want)) <= 1e-12 * scale.max(), (n, np.max(np.abs(got - want)) / scale.max())
+        seen.append(np.abs(want).max())
+
+    pc.check_adjoint_chain(orc, dut, c, HYB, 0.004, 1e-12, history, k5_hook=theta_check)
+    assert_allowances(used, net)
+    st = pc.load_history(orc, c, 0.004, history)
+    assert len(seen) == len(st) - 1 and max(seen) > 0.0
+    check_purpose(net, kind, history, [x for _, _, x in st])
+
+
+@pytest.mark.parametrize("npts", [1, 15, 16, 17, 1023, 1024, 1025, 3 * 1024 + 5])
+@pytest.mark.parametrize("name", ["tanh_16_16", "tanh_1", "sigmoid_64", "sigmoid_8_5_7"])
+def test_weight_gradient_at_chunk_and_block_edges(emu, name, npts):
+    # the kernel's chunks of 16 points and blocks of 1024 against autograd of the restated residual (non-saturated nets),
+    # and two runs bitwise equal
+    net = NETS[name]
+    rng = np.random.default_rng(npts)
+    xi = np.zeros((npts, 6))
+    xi[:, 0:3] = rng.normal(0.0, 4e-3, (npts, 3))
+    xi[:, 3], xi[:, 4] = 1.0, 1.0
+    xi[:, 5] = np.abs(rng.normal(0.0, 0.005, npts))
+    xi[-1, [0, 1, 2, 5]] = [0.01, 0.003, -0.008, 0.001]  # the last point, alone in its chunk or block, is plastic
+    phi = rng.normal(0.0, 1.0, (npts, 6))
+    got = emul_theta_gradient(emu, net, xi, phi)
+    assert got.tobytes() == emul_theta_gradient(emu, net, xi, phi).tobytes()
+    want = hr.theta_gradient(xi, phi, E, NU, Y, net.act, net.topo, net.s_in, net.s_out, net.theta, ABS_TOL)
+    assert np.max(np.abs(want)) > 0.0
+    assert np.max(np.abs(got - want)) <= 1e-12 * max(1, npts / 1024) * np.max(np.abs(want)) * 10, np.max(np.abs(got - want)) / np.max(np.abs(want))
+    # the last point alone decides the partial chunk / block: dropping it changes the result unless it is elastic
+    if npts > 1:
+        rest = emul_theta_gradient(emu, net, xi, phi, npts - 1)
+        last = hr.theta_gradient(xi[-1:], phi[-1:], E, NU, Y, net.act, net.topo, net.s_in, net.s_out, net.theta, ABS_TOL)
+        assert np.max(np.abs(got - rest - last)) <= 1e-11 * np.max(np.abs(want))

@@ -154,6 +154,27 @@ def test_notch2D_primal_with_linear_network_matches_hyper_J2_plane_stress():
     assert float(runs[1].xi[-1][..., 5].max()) > 0.0
 
 
+def test_notch2D_primal_with_tanh_network_matches_oracle_driver():
+    # PrimalDriver on notch2D with the nonlinear tanh [1,16,16,1] net of the catalogue against fe_driver.Primal run over
+    # the oracle's hybrid class: the global Newton iteration with its line search and the local solves inside it, four
+    # steps, up to alpha ~ 0.28 at the notch (the first layer deep in saturation there)
+    from calibr8_amd import Assembler
+    from calibr8_amd.primal import PrimalDriver
+    from fe_driver import Dbc, Primal
+    from hybrid_cases import HYB, NETS, hybrid_oracle
+    c, conn, ns = notch2d()
+    net = NETS["tanh_16_16"]
+    dbcs = notch_bcs(ns, 0.005)
+    asm = Assembler(3, c, conn, HYB, [E, NU, Y], max_iters=500, abs_tol=ABS_TOL, rel_tol=ABS_TOL, embedded=net.embedded())
+    drv = PrimalDriver(asm, dbcs, max_iters=30, abs_tol=1e-10, rel_tol=1e-10).solve(4)
+    orc, _, _ = hybrid_oracle((3, c, conn), net, max_iters=500)
+    ref = Primal(orc, c, [Dbc(*s) for s in dbcs], max_iters=30, abs_tol=1e-10, rel_tol=1e-10).solve(4)
+    assert drv.newton_iters == ref.newton_iters, (drv.newton_iters, ref.newton_iters)
+    J, Jr = drv.qoi(), ref.qoi()
+    assert abs(J - Jr) <= 1e-10 * abs(Jr), (J, Jr)
+    assert float(ref.xi[-1][..., 5].max()) > 0.1
+
+
 def test_notch2D_adjoint_gradient_with_network_passes_fd_check():
     # c8_adjoint_solve_step with theta appended to grad, against central differences of the device objective along
     # E, nu, Y and along a random theta direction (tanh [1, 16, 16, 1])
@@ -277,3 +298,78 @@ def test_million_triangles_step_matches_emulator_on_sampled_elements(tmp_path):
     assert L.c8emu_hybrid_call(1, len(nodes), 200, sc.ctypes.data_as(dp), sub.ctypes.data_as(ip), None, 1, 500, ABS_TOL,
                                ABS_TOL, P.ctypes.data_as(dp), act.ctypes.data_as(ip), nn_buf.ctypes.data_as(dp), ptrs) == 0
     assert np.max(np.abs(xi_d[sample] - xi_e)) <= 1e-12 * max(1.0, np.max(np.abs(xi_e)))
+
+
+# ---- the network catalogue (hybrid_cases.NETS) against the oracle's hybrid class, through the C ABI ----------------------
+DEVICE_RUNS = [(n, k, h) for n in ("tanh_1", "relu_zero_bias", "tanh_softening", "tanh_saturated", "sigmoid_saturated")
+               for k in ("structured", "notch2D") for h in ("proportional", "hold_unload", "reverse", "nonproportional",
+                                                            "unload_reload")] + \
+              [("tanh_widest", "structured", h) for h in ("proportional", "reverse")]
+
+
+@pytest.mark.parametrize("name,kind,history", DEVICE_RUNS)
+def test_catalogue_k1_to_k5_and_weight_gradient_against_oracle_on_device(name, kind, history):
+    # K1-K5 of the device kernels against the oracle's hybrid class at every step, and the theta tail of
+    # c8_param_gradient against the oracle's K5 along theta (the widest network: a sample of theta, see test_emul_hybrid)
+    import parity_cases as pc
+    from gpu_backend import GpuBackend
+    from hybrid_cases import HYB, NETS, assert_allowances, check_purpose, hybrid_oracle, oracle_theta_gradient, theta_sample
+    pc.ACTIVE.setdefault(HYB, [0, 1, 2])
+    net = NETS[name]
+    orc, c, conn = hybrid_oracle(kind, net)
+    dut = GpuBackend(3, c, conn, HYB, [E, NU, Y], embedded=net.embedded(), max_iters=500, abs_tol=ABS_TOL, rel_tol=ABS_TOL)
+    assert dut.asm.num_embedded_params == len(net.theta)
+    used = dict(pc.AUDIT.used)
+    pc.check_forward(orc, dut, c, HYB, 0.004, 1e-12, history)
+    pc.check_residual(orc, dut, c, 0.004, 1e-12, history)
+    idx = theta_sample(net) if name == "tanh_widest" else None
+    seen = []
+
+    def theta_check(n, step, z_u, z_p, phi):
+        want, scale = oracle_theta_gradient(orc, step, z_u, z_p, phi, idx)
+        got = dut.qoi_gradient(*step, z_u, z_p, phi, dut.asm.num_grad_params)[3:]
+        got = got if idx is None else got[idx]
+        assert np.max(np.abs(got - want)) <= 1e-12 * scale.max(), (n, np.max(np.abs(got - want)) / scale.max())
+        seen.append(np.abs(want).max())
+
+    pc.check_adjoint_chain(orc, dut, c, HYB, 0.004, 1e-12, history, k5_hook=theta_check)
+    assert_allowances(used, net)
+    assert seen and max(seen) > 0.0
+    check_purpose(net, kind, history, [x for _, _, x in pc.load_history(orc, c, 0.004, history)])
+
+
+@pytest.mark.parametrize("npts", [1, 15, 16, 17, 1023, 1024, 1025, 3 * 1024 + 5])
+def test_weight_gradient_kernel_at_chunk_and_block_edges_on_device(npts):
+    # tri3 has one point per element: a strip of npts triangles; the weight-gradient kernel against autograd of the
+    # restated residual (one-layer and two-layer nets), two runs bitwise equal
+    import torch
+    from hybrid_cases import NETS
+    ncell = (npts + 1) // 2
+    coords, conn = tri_mesh(ncell, 1)
+    conn = np.ascontiguousarray(conn[:npts])
+    rng = np.random.default_rng(npts)
+    for name in ("tanh_1", "tanh_16_16", "sigmoid_64"):
+        net = NETS[name]
+        a = hybrid(coords, conn, net.act, net.topo, net.s_in, net.s_out, net.theta)
+        assert a.nelems * a.npts == npts
+        xi = np.zeros((npts, 1, 6))
+        xi[..., 0:3] = rng.normal(0.0, 4e-3, (npts, 1, 3))
+        xi[..., 3], xi[..., 4] = 1.0, 1.0
+        xi[..., 5] = np.abs(rng.normal(0.0, 0.005, (npts, 1)))
+        xi[-1, 0, [0, 1, 2, 5]] = [0.01, 0.003, -0.008, 0.001]  # the last point, alone in its chunk or block, is plastic
+        phi = rng.normal(0.0, 1.0, (npts, 1, 6))
+        z = a.dev(np.zeros(coords.shape[0] * 2))
+        pz = a.dev(np.zeros(coords.shape[0]))
+        d_xi, d_phi = a.dev(xi), a.dev(phi)
+        grads = []
+        for _ in range(2):
+            g = a.dev(np.zeros(a.num_grad_params))
+            a.qoi_gradient(z, pz, z, pz, d_xi, d_xi, z, pz, d_phi, g)
+            torch.cuda.synchronize()
+            grads.append(g.cpu().numpy()[1:])
+        want = hr.theta_gradient(xi.reshape(npts, 6), phi.reshape(npts, 6), E, NU, Y, net.act, net.topo, net.s_in,
+                                 net.s_out, net.theta, ABS_TOL)
+        assert np.max(np.abs(want)) > 0.0
+        # the bar of the 6000-point test above: the NN(0) term summed per block against per point
+        assert np.max(np.abs(grads[0] - want)) <= 1e-11 * np.max(np.abs(want)), (name, npts)
+        assert grads[0].tobytes() == grads[1].tobytes()
