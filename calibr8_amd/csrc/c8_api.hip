@@ -37,30 +37,14 @@ template <class T> static int upload(T** dptr, std::vector<T> const& h) {
   return C8_OK;
 }
 
+// the row of the model table (c8_registry.hpp) named `name` on an ndims-D mesh: its id, NLOC and NPARAMS
 static int model_id(char const* name, int ndims, int* nloc, int* nparams) {
-  std::string const s = name ? name : "";
-  if (ndims == 2) {  // the models of the reference's 2-D decks that run on `mechanics` (2 + 1 equations per node)
-    if (s == "small_J2") { *nloc = SmallJ2Plane<double>::NLOC; *nparams = SmallJ2Plane<double>::NPARAMS; return MODEL_SMALL_J2; }
-    if (s == "small_hill_plane_strain") { *nloc = SmallHillPlaneStrain<double>::NLOC; *nparams = SmallHillPlaneStrain<double>::NPARAMS; return MODEL_SMALL_HILL_PLANE_STRAIN; }
-    if (s == "hypo_hill_plane_strain") { *nloc = HypoHillPlaneStrain<double>::NLOC; *nparams = HypoHillPlaneStrain<double>::NPARAMS; return MODEL_HYPO_HILL_PLANE_STRAIN; }
-    if (s == "hyper_J2_plane_strain") { *nloc = HyperJ2PlaneStrain<double>::NLOC; *nparams = HyperJ2PlaneStrain<double>::NPARAMS; return MODEL_HYPER_J2_PLANE_STRAIN; }
-    // the models of `mechanics_plane_stress` (2 equations per node, no pressure)
-    if (s == "small_hill_plane_stress") { *nloc = SmallHillPlaneStress<double>::NLOC; *nparams = SmallHillPlaneStress<double>::NPARAMS; return MODEL_SMALL_HILL_PLANE_STRESS; }
-    if (s == "hyper_J2_plane_stress") { *nloc = HyperJ2PlaneStress<double>::NLOC; *nparams = HyperJ2PlaneStress<double>::NPARAMS; return MODEL_HYPER_J2_PLANE_STRESS; }
-    if (s == "hypo_hill_plane_stress") { *nloc = HypoHillPlaneStress<double>::NLOC; *nparams = HypoHillPlaneStress<double>::NPARAMS; return MODEL_HYPO_HILL_PLANE_STRESS; }
-    if (s == "hybrid_hyper_J2_plane_stress") { *nloc = HybridHyperJ2PlaneStress<double>::NLOC; *nparams = HybridHyperJ2PlaneStress<double>::NPARAMS; return MODEL_HYBRID_HYPER_J2_PLANE_STRESS; }
-    return MODEL_NONE;
-  }
-  if (s == "elastic") { *nloc = Elastic<double>::NLOC; *nparams = Elastic<double>::NPARAMS; return MODEL_ELASTIC; }
-  if (s == "small_J2") { *nloc = SmallJ2<double>::NLOC; *nparams = SmallJ2<double>::NPARAMS; return MODEL_SMALL_J2; }
-  if (s == "hyper_J2") { *nloc = HyperJ2<double>::NLOC; *nparams = HyperJ2<double>::NPARAMS; return MODEL_HYPER_J2; }
-  if (s == "isotropic_elastic") { *nloc = IsotropicElastic<double>::NLOC; *nparams = IsotropicElastic<double>::NPARAMS; return MODEL_ISOTROPIC_ELASTIC; }
-  if (s == "hypo_hill") { *nloc = HypoHill<double>::NLOC; *nparams = HypoHill<double>::NPARAMS; return MODEL_HYPO_HILL; }
-  if (s == "small_hill") { *nloc = SmallHill<double>::NLOC; *nparams = SmallHill<double>::NPARAMS; return MODEL_SMALL_HILL; }
-  if (s == "small_hosford") { *nloc = SmallHosford<double>::NLOC; *nparams = SmallHosford<double>::NPARAMS; return MODEL_SMALL_HOSFORD; }
-  if (s == "hypo_hosford") { *nloc = HypoHosford<double>::NLOC; *nparams = HypoHosford<double>::NPARAMS; return MODEL_HYPO_HOSFORD; }
-  if (s == "hypo_barlat") { *nloc = HypoBarlat<double>::NLOC; *nparams = HypoBarlat<double>::NPARAMS; return MODEL_HYPO_BARLAT; }
-  return MODEL_NONE;
+  int id = MODEL_NONE;
+  visit_models([&](auto row) {
+    using M = typename decltype(row)::Real;
+    if (row.dim == ndims && name && std::strcmp(row.name, name) == 0) { id = row.id; *nloc = M::NLOC; *nparams = M::NPARAMS; }
+  });
+  return id;
 }
 
 static void stage_release(c8_ctx* c);
@@ -237,28 +221,13 @@ int c8_graph(const c8_ctx* c, int i, int j, int64_t* rowptr, int32_t* colidx) {
 int c8_init_variables(const c8_ctx* c, double* xi) {
   if (!c || !xi) return fail(C8_ERR_ARG, "c8_init_variables: bad argument");
   size_t const npt = (size_t)c->mesh.nelems * c->npts0;
-  for (size_t q = 0; q < npt; ++q) {
-    double* x = xi + q * c->nloc;
-    switch (c->model) {  // init_variables_impl of each model
-      case MODEL_ELASTIC: Elastic<double>::init_variables(x); break;
-      case MODEL_SMALL_J2: if (c->ndims == 2) SmallJ2Plane<double>::init_variables(x); else SmallJ2<double>::init_variables(x); break;
-      case MODEL_SMALL_HILL_PLANE_STRAIN: SmallHillPlaneStrain<double>::init_variables(x); break;
-      case MODEL_HYPER_J2_PLANE_STRAIN: HyperJ2PlaneStrain<double>::init_variables(x); break;
-      case MODEL_HYPO_HILL_PLANE_STRAIN: HypoHillPlaneStrain<double>::init_variables(x); break;
-      case MODEL_SMALL_HILL_PLANE_STRESS: SmallHillPlaneStress<double>::init_variables(x); break;
-      case MODEL_HYPER_J2_PLANE_STRESS: HyperJ2PlaneStress<double>::init_variables(x); break;
-      case MODEL_HYBRID_HYPER_J2_PLANE_STRESS: HybridHyperJ2PlaneStress<double>::init_variables(x); break;
-      case MODEL_HYPO_HILL_PLANE_STRESS: HypoHillPlaneStress<double>::init_variables(x); break;
-      case MODEL_HYPER_J2: HyperJ2<double>::init_variables(x); break;
-      case MODEL_SMALL_HILL: SmallHill<double>::init_variables(x); break;
-      case MODEL_ISOTROPIC_ELASTIC: IsotropicElastic<double>::init_variables(x); break;
-      case MODEL_HYPO_HILL: HypoHill<double>::init_variables(x); break;
-      case MODEL_SMALL_HOSFORD: SmallHosford<double>::init_variables(x); break;
-      case MODEL_HYPO_HOSFORD: HypoHosford<double>::init_variables(x); break;
-      case MODEL_HYPO_BARLAT: HypoBarlat<double>::init_variables(x); break;
-      default: return fail(C8_ERR_UNSUPPORTED, "c8_init_variables: unknown model");
-    }
-  }
+  bool known = false;
+  visit_models([&](auto row) {  // init_variables_impl of the context's model
+    if (row.id != c->model || row.dim != c->ndims) return;
+    known = true;
+    for (size_t q = 0; q < npt; ++q) decltype(row)::Real::init_variables(xi + q * c->nloc);
+  });
+  if (!known) return fail(C8_ERR_UNSUPPORTED, "c8_init_variables: unknown model");
   return C8_OK;
 }
 

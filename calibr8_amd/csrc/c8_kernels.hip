@@ -750,7 +750,7 @@ template <template <class> class ModelT> struct WaveKernel<Elem<C8_HEX8>, ModelT
   static constexpr hipError_t (*shape_tables)(MeshTables const&, double*, int, hipStream_t) = &launch_shape_tables<Elem<C8_HEX8>>;
 };
 
-template <class E, template <class> class ModelT> static KernelSet kernel_set() {
+template <class E, template <class> class ModelT> static KernelSet kernel_set(ModelTag<ModelT>) {
   using WK = WaveKernel<E, ModelT>;
   KernelSet ks;
   ks.forward_jacobian = &launch_forward<E, ModelT>;
@@ -778,77 +778,48 @@ template <class E, template <class> class ModelT> static KernelSet kernel_set() 
   return ks;
 }
 
-// The registry: one line per constitutive model (local_residual.cpp:893-933).  The instantiations are compiled in
+// The registry: the kernel sets of the rows of the model table (c8_registry.hpp).  The instantiations are compiled in
 // PARTS -- this file is compiled once per part with -DC8_KERNEL_PART=n (calibr8_amd/build.py, in parallel) and once as a
-// whole by the tools that read its assembly; every part is a function the registry of part 0 dispatches to.
+// whole by the tools that read its assembly; the table gives the part of each row on each element type.
 #ifndef C8_KERNEL_PART
 #define C8_KERNEL_PART -1  // all parts in this translation unit
 #endif
 #define C8_PART(n) (C8_KERNEL_PART == -1 || C8_KERNEL_PART == (n))
-KernelSet kernels_hex8_a(int model);       // part 0: elastic, small_J2, isotropic_elastic (+ get_kernels)
-KernelSet kernels_hex8_b(int model);       // part 1: hyper_J2, small_hill
-KernelSet kernels_hex8_c(int model);       // part 2: hypo_hill
-KernelSet kernels_tet4(int model);         // part 3: the six models on tet4
-KernelSet kernels_2d(int model);           // part 4: tri3 under mechanics and mechanics_plane_stress
-KernelSet kernels_line_search(int elem_type, int model);  // part 5: Hosford / Barlat on tet4 and hex8
-
-#if C8_PART(0)
-KernelSet kernels_hex8_a(int model) {
-  using E = Elem<C8_HEX8>;
-  switch (model) {
-    case MODEL_ELASTIC: return kernel_set<E, Elastic>();
-    case MODEL_SMALL_J2: return kernel_set<E, SmallJ2>();
-    case MODEL_ISOTROPIC_ELASTIC: return kernel_set<E, IsotropicElastic>();
-  }
-  return KernelSet{};
+template <int P> static KernelSet part_kernels(int elem_type, int model) {
+  KernelSet ks;
+  // hex8 before the other elements: the kernels of a part come out grouped by element, and the labels of their assembly
+  // (numbered in order of instantiation) stay comparable between builds
+  visit_models([&](auto row) {
+    if constexpr (decltype(row)::hex8_part == P) { if (elem_type == C8_HEX8 && row.id == model) ks = kernel_set<Elem<C8_HEX8>>(row); }
+  });
+  visit_models([&](auto row) {
+    using R = decltype(row);
+    if constexpr (R::tet4_part == P) { if (elem_type == C8_TET4 && row.id == model) ks = kernel_set<Elem<C8_TET4>>(row); }
+    if constexpr (R::tri3_part == P) { if (elem_type == C8_TRI3 && row.id == model) ks = kernel_set<typename R::Elem2D>(row); }
+  });
+  return ks;
 }
+// one entry point per part, defined in the part's translation unit
+KernelSet kernels_part0(int elem_type, int model);
+KernelSet kernels_part1(int elem_type, int model);
+KernelSet kernels_part2(int elem_type, int model);
+KernelSet kernels_part3(int elem_type, int model);
+KernelSet kernels_part4(int elem_type, int model);
+KernelSet kernels_part5(int elem_type, int model);
+#if C8_PART(0)
+KernelSet kernels_part0(int elem_type, int model) { return part_kernels<0>(elem_type, model); }
 #endif
 #if C8_PART(1)
-KernelSet kernels_hex8_b(int model) {
-  using E = Elem<C8_HEX8>;
-  switch (model) {
-    case MODEL_HYPER_J2: return kernel_set<E, HyperJ2>();
-    case MODEL_SMALL_HILL: return kernel_set<E, SmallHill>();
-  }
-  return KernelSet{};
-}
+KernelSet kernels_part1(int elem_type, int model) { return part_kernels<1>(elem_type, model); }
 #endif
 #if C8_PART(2)
-KernelSet kernels_hex8_c(int model) {
-  if (model == MODEL_HYPO_HILL) return kernel_set<Elem<C8_HEX8>, HypoHill>();
-  return KernelSet{};
-}
+KernelSet kernels_part2(int elem_type, int model) { return part_kernels<2>(elem_type, model); }
 #endif
 #if C8_PART(3)
-KernelSet kernels_tet4(int model) {
-  using E = Elem<C8_TET4>;
-  switch (model) {
-    case MODEL_ELASTIC: return kernel_set<E, Elastic>();
-    case MODEL_SMALL_J2: return kernel_set<E, SmallJ2>();
-    case MODEL_HYPER_J2: return kernel_set<E, HyperJ2>();
-    case MODEL_SMALL_HILL: return kernel_set<E, SmallHill>();
-    case MODEL_ISOTROPIC_ELASTIC: return kernel_set<E, IsotropicElastic>();
-    case MODEL_HYPO_HILL: return kernel_set<E, HypoHill>();
-  }
-  return KernelSet{};
-}
+KernelSet kernels_part3(int elem_type, int model) { return part_kernels<3>(elem_type, model); }
 #endif
 #if C8_PART(4)
-// 2-D meshes: the models the reference's 2-D decks run on `mechanics` with 2 + 1 equations per node ...
-KernelSet kernels_2d(int model) {
-  switch (model) {
-    case MODEL_SMALL_J2: return kernel_set<Elem<C8_TRI3>, SmallJ2Plane>();
-    case MODEL_SMALL_HILL_PLANE_STRAIN: return kernel_set<Elem<C8_TRI3>, SmallHillPlaneStrain>();
-    case MODEL_HYPER_J2_PLANE_STRAIN: return kernel_set<Elem<C8_TRI3>, HyperJ2PlaneStrain>();
-    case MODEL_HYPO_HILL_PLANE_STRAIN: return kernel_set<Elem<C8_TRI3>, HypoHillPlaneStrain>();
-    // ... and `mechanics_plane_stress`: one residual, six element DOFs
-    case MODEL_SMALL_HILL_PLANE_STRESS: return kernel_set<Tri3PlaneStress, SmallHillPlaneStress>();
-    case MODEL_HYPER_J2_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HyperJ2PlaneStress>();
-    case MODEL_HYPO_HILL_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HypoHillPlaneStress>();
-    case MODEL_HYBRID_HYPER_J2_PLANE_STRESS: return kernel_set<Tri3PlaneStress, HybridHyperJ2PlaneStress>();
-  }
-  return KernelSet{};
-}
+KernelSet kernels_part4(int elem_type, int model) { return part_kernels<4>(elem_type, model); }
 
 // the weight gradient of the embedded network (c8_assemble_nn.hpp): one block per NN_GRAD_POINTS points, then one thread
 // per theta entry adds the partial rows in block order
@@ -876,31 +847,16 @@ hipError_t launch_nn_param_gradient(NnGradArgs const& ga, double* out, hipStream
 }
 #endif
 #if C8_PART(5)
-template <class E> static KernelSet line_search_set(int model) {
-  switch (model) {
-    case MODEL_SMALL_HOSFORD: return kernel_set<E, SmallHosford>();
-    case MODEL_HYPO_HOSFORD: return kernel_set<E, HypoHosford>();
-    case MODEL_HYPO_BARLAT: return kernel_set<E, HypoBarlat>();
-  }
-  return KernelSet{};
-}
-KernelSet kernels_line_search(int elem_type, int model) {
-  return elem_type == C8_HEX8 ? line_search_set<Elem<C8_HEX8>>(model) : line_search_set<Elem<C8_TET4>>(model);
-}
+KernelSet kernels_part5(int elem_type, int model) { return part_kernels<5>(elem_type, model); }
 #endif
 
 #if C8_PART(0)
 KernelSet get_kernels(int elem_type, int model) {
-  if (elem_type == C8_TRI3) return kernels_2d(model);
-  if ((model >= MODEL_SMALL_HILL_PLANE_STRAIN && model <= MODEL_HYPO_HILL_PLANE_STRESS) || model == MODEL_HYBRID_HYPER_J2_PLANE_STRESS)
-    return KernelSet{};  // the plane models exist on 2-D meshes only
-  if (elem_type != C8_HEX8 && elem_type != C8_TET4) return KernelSet{};
-  if (model >= MODEL_SMALL_HOSFORD) return kernels_line_search(elem_type, model);
-  if (elem_type == C8_TET4) return kernels_tet4(model);
-  KernelSet ks = kernels_hex8_a(model);
-  if (!ks.forward_jacobian) ks = kernels_hex8_b(model);
-  if (!ks.forward_jacobian) ks = kernels_hex8_c(model);
-  return ks;
+  for (auto part : {kernels_part0, kernels_part1, kernels_part2, kernels_part3, kernels_part4, kernels_part5}) {
+    KernelSet const ks = part(elem_type, model);
+    if (ks.forward_jacobian) return ks;
+  }
+  return KernelSet{};
 }
 #endif
 

@@ -6,16 +6,9 @@
 #include "c8_assemble_adjoint.hpp"
 #include "c8_assemble_vfm.hpp"
 #include "c8_assemble_nn.hpp"
+#include "c8_registry.hpp"
 
 namespace c8 {
-
-enum { MODEL_NONE = -1, MODEL_ELASTIC = 0, MODEL_SMALL_J2 = 1, MODEL_HYPER_J2 = 2, MODEL_SMALL_HILL = 3, MODEL_ISOTROPIC_ELASTIC = 4, MODEL_HYPO_HILL = 5,
-       MODEL_SMALL_HILL_PLANE_STRAIN = 6, MODEL_HYPER_J2_PLANE_STRAIN = 7, MODEL_HYPO_HILL_PLANE_STRAIN = 8,
-       MODEL_SMALL_HILL_PLANE_STRESS = 9, MODEL_HYPER_J2_PLANE_STRESS = 10, MODEL_HYPO_HILL_PLANE_STRESS = 11,
-       MODEL_SMALL_HOSFORD = 12, MODEL_HYPO_HOSFORD = 13, MODEL_HYPO_BARLAT = 14, MODEL_HYBRID_HYPER_J2_PLANE_STRESS = 15 };
-inline bool model_is_plane_stress(int m) {
-  return (m >= MODEL_SMALL_HILL_PLANE_STRESS && m <= MODEL_HYPO_HILL_PLANE_STRESS) || m == MODEL_HYBRID_HYPER_J2_PLANE_STRESS;
-}
 
 struct LaunchArgs {
   MeshTables mt;
@@ -68,8 +61,7 @@ struct KernelSet {
 // then out[0 .. ntheta) += their sum in block order
 hipError_t launch_nn_param_gradient(NnGradArgs const& ga, double* out, hipStream_t stream);
 
-// registry keyed like the reference's string factories
-// (global_residual.cpp:620-630, local_residual.cpp:893-933)
+// the kernels of a row of the model table (c8_registry.hpp) on an element type; empty if there is none
 KernelSet get_kernels(int elem_type, int model);
 
 }  // namespace c8

@@ -13,7 +13,7 @@
 //     weak form as point fluxes: R(i,n,eq) += [V(i,eq) N_n + G(i,eq,:).grad N_n] w dv
 //
 // A new constitutive model is one struct implementing the LocalResidual
-// concept plus one line in C8_FOR_EACH_MODEL (c8_kernels.hip).
+// concept plus one row in C8_MODEL_TABLE (c8_registry.hpp).
 //
 // Semantics that must not be "simplified" (SURVEY.md section 10): the yield function is
 // scaled by val(mu), not mu (small_J2.cpp:208, hyper_J2.cpp:264); the branch

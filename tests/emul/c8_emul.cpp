@@ -17,6 +17,7 @@
 #include "../../calibr8_amd/csrc/c8_assemble_node.hpp"
 #include "../../calibr8_amd/csrc/c8_host.hpp"
 #include "../../calibr8_amd/csrc/c8_qoi_host.hpp"
+#include "../../calibr8_amd/csrc/c8_registry.hpp"
 
 using namespace c8;
 
@@ -285,15 +286,11 @@ template <template <class> class ModelT, bool MANY> static void run_node_rows_as
   delete sh;
 }
 template <template <class> class ModelT> static int run_node_rows(Call const& c) {
-  if constexpr (has_closed_form_rows<ModelT<Dual>>::value) {
-    if (!c.mt.shape || c.graph->max_degree > GATHER_MAX_DEGREE) return -4;
-    // the library's choice (launch_node_rows); g_node_many forces the form for nodes with more than eight elements
-    if (c.graph->max_node_elems > 8 || g_node_many) run_node_rows_as<ModelT, true>(c);
-    else run_node_rows_as<ModelT, false>(c);
-    return 0;
-  } else {
-    return -4;
-  }
+  if (!c.mt.shape || c.graph->max_degree > GATHER_MAX_DEGREE) return -4;
+  // the library's choice (launch_node_rows); g_node_many forces the form for nodes with more than eight elements
+  if (c.graph->max_node_elems > 8 || g_node_many) run_node_rows_as<ModelT, true>(c);
+  else run_node_rows_as<ModelT, false>(c);
+  return 0;
 }
 
 template <template <class> class ModelT> static void run_residual_wave(Call const& c) {
@@ -316,106 +313,39 @@ template <template <class> class ModelT> static void run_qoi_wave(Call const& c)
   delete sh;
 }
 
-// 2-D meshes (tri3): the slot kernels with the 2-D models
-static int dispatch_2d(std::string const& model, Call const& c) {
-  using E = Elem<C8_TRI3>;
-  if (c.what != K_FORWARD && c.what != K_RESIDUAL && c.what != K_ADJ_JAC && c.what != K_ADJ_LOCAL && c.what != K_GRAD && c.what != K_QOI) return -4;
-  if (c.staged) return -4;
-  if (model == "small_J2") run<E, SmallJ2Plane>(c);
-  else if (model == "small_hill_plane_strain") run<E, SmallHillPlaneStrain>(c);
-  else if (model == "hyper_J2_plane_strain") run<E, HyperJ2PlaneStrain>(c);
-  else if (model == "hypo_hill_plane_strain") run<E, HypoHillPlaneStrain>(c);
-  // `mechanics_plane_stress`: one residual, six element DOFs
-  else if (model == "small_hill_plane_stress") run<Tri3PlaneStress, SmallHillPlaneStress>(c);
-  else if (model == "hyper_J2_plane_stress") run<Tri3PlaneStress, HyperJ2PlaneStress>(c);
-  else if (model == "hypo_hill_plane_stress") run<Tri3PlaneStress, HypoHillPlaneStress>(c);
-  else return -2;
-  return 0;
-}
-
-template <class E> static int dispatch(std::string const& model, Call const& c) {
-  if (c.what == K_FORWARD_NODE || c.what == K_ADJ_JAC_NODE) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if (model == "small_J2") return run_node_rows<SmallJ2>(c);
-    return -4;
+// the kernel form c.what of a row of the model table on element E, where the library builds it (c8_kernels.hip:
+// kernel_set): the lane-group kernels on every element, staged on 3-D ones only; the wave kernels on hex8; the row-per-node
+// kernels and K4 / K5 in closed form where the model has closed-form rows, on hex8.  -4: no such form.
+template <class E, template <class> class ModelT> static int run_form(Call const& c, ModelTag<ModelT>) {
+  constexpr bool hex8 = E::TYPE == C8_HEX8, closed_rows = hex8 && has_closed_form_rows<ModelT<Dual>>::value;
+  switch (c.what) {
+    case K_FORWARD_NODE:
+    case K_ADJ_JAC_NODE:
+      if constexpr (closed_rows) return run_node_rows<ModelT>(c);
+      return -4;
+    case K_ADJ_LOCAL_CLOSED:
+      if constexpr (closed_rows) { run_adjoint_local_closed<ModelT>(c); return 0; }
+      return -4;
+    case K_GRAD_CLOSED:
+      if constexpr (closed_rows) { run_param_gradient_closed<ModelT>(c); return 0; }
+      return -4;
+    case K_QOI_WAVE:
+      if constexpr (hex8) { run_qoi_wave<ModelT>(c); return 0; }
+      return -4;
+    case K_RESIDUAL_WAVE:
+      if constexpr (hex8) { run_residual_wave<ModelT>(c); return 0; }
+      return -4;
+    case K_ADJ_LOCAL_WAVE:
+    case K_GRAD_WAVE:
+      if constexpr (hex8) { run_wave_adjoint<ModelT>(c); return 0; }
+      return -4;
+    case K_FORWARD_WAVE:
+    case K_ADJ_JAC_WAVE:
+      if constexpr (hex8) { run_wave<ModelT>(c); return 0; }
+      return -4;
   }
-  if (c.what == K_ADJ_LOCAL_CLOSED || c.what == K_GRAD_CLOSED) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if constexpr (E::TYPE == C8_HEX8) {
-      if (model == "small_J2") {
-        if (c.what == K_GRAD_CLOSED) run_param_gradient_closed<SmallJ2>(c);
-        else run_adjoint_local_closed<SmallJ2>(c);
-        return 0;
-      }
-    }
-    return -4;
-  }
-  if (c.what == K_QOI_WAVE) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if (model == "elastic") run_qoi_wave<Elastic>(c);
-    else if (model == "small_J2") run_qoi_wave<SmallJ2>(c);
-    else if (model == "hyper_J2") run_qoi_wave<HyperJ2>(c);
-    else if (model == "small_hill") run_qoi_wave<SmallHill>(c);
-    else if (model == "isotropic_elastic") run_qoi_wave<IsotropicElastic>(c);
-    else if (model == "hypo_hill") run_qoi_wave<HypoHill>(c);
-    else if (model == "small_hosford") run_qoi_wave<SmallHosford>(c);
-    else if (model == "hypo_hosford") run_qoi_wave<HypoHosford>(c);
-    else if (model == "hypo_barlat") run_qoi_wave<HypoBarlat>(c);
-    else return -2;
-    return 0;
-  }
-  if (c.what == K_RESIDUAL_WAVE) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if (model == "elastic") run_residual_wave<Elastic>(c);
-    else if (model == "small_J2") run_residual_wave<SmallJ2>(c);
-    else if (model == "hyper_J2") run_residual_wave<HyperJ2>(c);
-    else if (model == "small_hill") run_residual_wave<SmallHill>(c);
-    else if (model == "isotropic_elastic") run_residual_wave<IsotropicElastic>(c);
-    else if (model == "hypo_hill") run_residual_wave<HypoHill>(c);
-    else if (model == "small_hosford") run_residual_wave<SmallHosford>(c);
-    else if (model == "hypo_hosford") run_residual_wave<HypoHosford>(c);
-    else if (model == "hypo_barlat") run_residual_wave<HypoBarlat>(c);
-    else return -2;
-    return 0;
-  }
-  if (c.what == K_ADJ_LOCAL_WAVE || c.what == K_GRAD_WAVE) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if (model == "elastic") run_wave_adjoint<Elastic>(c);
-    else if (model == "small_J2") run_wave_adjoint<SmallJ2>(c);
-    else if (model == "hyper_J2") run_wave_adjoint<HyperJ2>(c);
-    else if (model == "small_hill") run_wave_adjoint<SmallHill>(c);
-    else if (model == "isotropic_elastic") run_wave_adjoint<IsotropicElastic>(c);
-    else if (model == "hypo_hill") run_wave_adjoint<HypoHill>(c);
-    else if (model == "small_hosford") run_wave_adjoint<SmallHosford>(c);
-    else if (model == "hypo_hosford") run_wave_adjoint<HypoHosford>(c);
-    else if (model == "hypo_barlat") run_wave_adjoint<HypoBarlat>(c);
-    else return -2;
-    return 0;
-  }
-  if (c.what == K_FORWARD_WAVE || c.what == K_ADJ_JAC_WAVE) {
-    if (E::TYPE != C8_HEX8) return -4;
-    if (model == "elastic") run_wave<Elastic>(c);
-    else if (model == "small_J2") run_wave<SmallJ2>(c);
-    else if (model == "hyper_J2") run_wave<HyperJ2>(c);
-    else if (model == "small_hill") run_wave<SmallHill>(c);
-    else if (model == "isotropic_elastic") run_wave<IsotropicElastic>(c);
-    else if (model == "hypo_hill") run_wave<HypoHill>(c);
-    else if (model == "small_hosford") run_wave<SmallHosford>(c);
-    else if (model == "hypo_hosford") run_wave<HypoHosford>(c);
-    else if (model == "hypo_barlat") run_wave<HypoBarlat>(c);
-    else return -2;
-    return 0;
-  }
-  if (model == "elastic") run<E, Elastic>(c);
-  else if (model == "small_J2") run<E, SmallJ2>(c);
-  else if (model == "hyper_J2") run<E, HyperJ2>(c);
-  else if (model == "small_hill") run<E, SmallHill>(c);
-  else if (model == "isotropic_elastic") run<E, IsotropicElastic>(c);
-  else if (model == "hypo_hill") run<E, HypoHill>(c);
-  else if (model == "small_hosford") run<E, SmallHosford>(c);
-  else if (model == "hypo_hosford") run<E, HypoHosford>(c);
-  else if (model == "hypo_barlat") run<E, HypoBarlat>(c);
-  else return -2;
+  if (E::DIM == 2 && (c.staged || c.what < K_FORWARD || c.what > K_QOI)) return -4;
+  run<E, ModelT>(c);
   return 0;
 }
 
@@ -472,8 +402,15 @@ extern "C" int c8emu_call(int what, int elem_type, int nnodes, int nelems, doubl
   c.sa = SystemArgs{{{ptrs[6], ptrs[7]}, {ptrs[8], ptrs[9]}}, {ptrs[10], ptrs[11]}, &status, 0};
   c.aa = AdjointArgs{ptrs[12], ptrs[13], ptrs[14], ptrs[15], ptrs[16], ptrs[17], active, QoiArgs{1., 0., 0, nullptr, elem_type == C8_TRI3 ? 2. : 3.}};
   auto run_it = [&]() {
-    if (elem_type == C8_TRI3) return dispatch_2d(local_type, c);
-    return (elem_type == C8_HEX8) ? dispatch<Elem<C8_HEX8>>(local_type, c) : dispatch<Elem<C8_TET4>>(local_type, c);
+    int rc = -2;  // not a row of the model table
+    visit_models([&](auto row) {
+      using R = decltype(row);
+      if (row.dim != (elem_type == C8_TRI3 ? 2 : 3) || std::strcmp(row.name, local_type) != 0) return;
+      if constexpr (has_embedded<typename R::Real>::value) return;  // the network's buffer: c8emu_hybrid_call
+      else if constexpr (R::dim == 2) rc = run_form<typename R::Elem2D>(c, row);
+      else rc = elem_type == C8_HEX8 ? run_form<Elem<C8_HEX8>>(c, row) : run_form<Elem<C8_TET4>>(c, row);
+    });
+    return rc;
   };
   int const base = c.what;
   bool const is_qoi = base == K_QOI || base == K_QOI_WAVE, is_k3 = base == K_ADJ_JAC || base == K_ADJ_JAC_WAVE || base == K_ADJ_JAC_NODE,

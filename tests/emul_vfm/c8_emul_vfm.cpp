@@ -10,7 +10,7 @@
 enum { VFM_POWER = 0, VFM_FORWARD_SENS = 1, VFM_ADJOINT = 2 };
 
 template <template <class> class ModelT>
-static int vfm_run(int what, Call const& c, VfmArgs const& va, double* ivw, double* grad) {
+static void vfm_run(ModelTag<ModelT>, int what, Call const& c, VfmArgs const& va, double* ivw, double* grad) {
   using E = Tri3PlaneStress;
   GroupShared<E, ModelT<Dual>::NLOC> sh;
   auto* ex = new CpuExec<VfmLane<E, ModelT>, E::NDOF>();
@@ -25,7 +25,6 @@ static int vfm_run(int what, Call const& c, VfmArgs const& va, double* ivw, doub
     }
   }
   delete ex;
-  return 0;
 }
 
 // ptrs: 0 u, 1 u_prev, 2 xi_prev, 3 xi, 4 w, 5 b (or null), 6 S_prev (or null), 7 S, 8 h, 9 ivw, 10 grad
@@ -54,10 +53,13 @@ extern "C" int c8emu_vfm(int what, int nnodes, int nelems, double const* coords,
   VfmArgs const va{ptrs[4], ptrs[6], ptrs[7], ptrs[8], cm, active, nact};
   double* ivw = what == VFM_ADJOINT ? nullptr : ptrs[9];
   double* grad = what == VFM_POWER ? nullptr : ptrs[10];
-  std::string const model = local_type;
-  if (model == "small_hill_plane_stress") vfm_run<SmallHillPlaneStress>(what, c, va, ivw, grad);
-  else if (model == "hyper_J2_plane_stress") vfm_run<HyperJ2PlaneStress>(what, c, va, ivw, grad);
-  else if (model == "hypo_hill_plane_stress") vfm_run<HypoHillPlaneStress>(what, c, va, ivw, grad);
-  else return -2;
+  bool known = false;
+  visit_models([&](auto row) {  // the plane-stress rows of the model table, but those with network weights (as the library)
+    using R = decltype(row);
+    if constexpr (R::plane_stress && !has_embedded<typename R::Real>::value) {
+      if (std::strcmp(row.name, local_type) == 0) { vfm_run(row, what, c, va, ivw, grad); known = true; }
+    }
+  });
+  if (!known) return -2;
   return status ? -1 : 0;
 }

@@ -73,6 +73,58 @@ def test_no_cpu_fallback():
     assert b"unknown local residual name" in L.c8_last_error()
 
 
+def test_create_accepts_the_models_of_each_mesh_and_global_residual():
+    """c8_create over every local residual name on every element type, under both global residuals: a valid combination
+    passes the argument checks (no GPU: C8_ERR_DEVICE; a GPU: a context with one or two residuals), a wrong parameter
+    count is an argument error, and a name on the wrong mesh dimension or under the wrong global residual is refused"""
+    import torch
+    from calibr8_amd import lib
+    from meshes import brick, tri_mesh
+    L = lib.load_library()
+    gpu = torch.cuda.is_available()
+    hex_c, hex_conn, _ = brick(1, 1, 1)
+    tri_c, tri_conn, _ = tri_mesh(1, 1)
+    tet_c, tet_conn = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]]), np.array([[0, 1, 2, 3]], dtype=np.int32)
+    meshes = {lib.C8_ELEM_HEX8: (hex_c, hex_conn), lib.C8_ELEM_TET4: (tet_c, tet_conn), lib.C8_ELEM_TRI3: (tri_c, tri_conn)}
+    solid = {"elastic": 4, "small_J2": 6, "hyper_J2": 8, "isotropic_elastic": 2, "hypo_hill": 11, "small_hill": 11,
+             "small_hosford": 7, "hypo_hosford": 7, "hypo_barlat": 25}
+    plane = {"small_J2": 6, "small_hill_plane_strain": 9, "hyper_J2_plane_strain": 6, "hypo_hill_plane_strain": 9}
+    plane_stress = {"small_hill_plane_stress": 9, "hyper_J2_plane_stress": 8, "hypo_hill_plane_stress": 13,
+                    "hybrid_hyper_J2_plane_stress": 3}
+    valid = {(lib.C8_ELEM_HEX8, "mechanics"): solid, (lib.C8_ELEM_TET4, "mechanics"): solid,
+             (lib.C8_ELEM_TRI3, "mechanics"): plane, (lib.C8_ELEM_TRI3, "mechanics_plane_stress"): plane_stress}
+    names = sorted(set(solid) | set(plane) | set(plane_stress))
+
+    def create(et, global_type, name, nparams):
+        c, conn = meshes[et]
+        params = np.ones(nparams)
+        md = lib.MeshDesc(et, len(c), len(conn), 1, c.ctypes.data_as(lib.dp), conn.ctypes.data_as(lib.i32p), None, 0, None)
+        mo = lib.ModelDesc(global_type.encode(), name.encode(), 1.0, 10, 1e-12, 1e-12, nparams, params.ctypes.data_as(lib.dp))
+        h = C.c_void_p()
+        return L.c8_create(C.byref(md), C.byref(mo), C.byref(h)), h
+
+    for et in meshes:
+        for global_type in ("mechanics", "mechanics_plane_stress"):
+            table = valid.get((et, global_type), {})
+            for name in names:
+                case = (et, global_type, name)
+                if name not in table:
+                    rc, h = create(et, global_type, name, 6)
+                    assert rc == lib.C8_ERR_UNSUPPORTED and not h.value, case
+                    continue
+                n = table[name]
+                rc, h = create(et, global_type, name, n)
+                if gpu:
+                    assert rc == lib.C8_OK and h.value, (case, L.c8_last_error())
+                    assert L.c8_num_residuals(h) == (1 if global_type == "mechanics_plane_stress" else 2), case
+                    L.c8_destroy(h)
+                else:
+                    assert rc == lib.C8_ERR_DEVICE and not h.value, (case, L.c8_last_error())
+                for wrong in (n - 1, n + 1):
+                    rc, h = create(et, global_type, name, wrong)
+                    assert rc == lib.C8_ERR_ARG and not h.value, (case, wrong)
+
+
 def test_product_does_not_reference_the_oracle_or_emulator():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "calibr8_amd")):
         for f in files:
