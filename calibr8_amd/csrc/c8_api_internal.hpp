@@ -94,6 +94,12 @@ struct c8_ctx {
   double* d_nn = nullptr;
   double* d_nn_part = nullptr;       // per-block partial rows of the weight-gradient kernel
   size_t nn_part_n = 0;
+  // device-resident Krylov solve (c8_krylov.hip): node-block Jacobi inverses, work vectors, dot partials and scalars
+  double* d_kry_minv = nullptr;      // [nnodes][NB * NB]
+  double* d_kry_vec = nullptr;       // nine vectors of the system's length (x, r, rhat, p, v, s, t, phat, shat)
+  double* d_kry_part = nullptr;      // per-block partial sums of the inner products
+  void* d_kry_scalars = nullptr;     // rho, alpha, omega, beta, |r|^2, stop flag, iteration count (+ the set-up kernel's flag)
+  size_t kry_minv_n = 0, kry_vec_n = 0, kry_part_n = 0;
 };
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
 int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);

@@ -1,0 +1,559 @@
+// c8_krylov.hip -- the device-resident linear solve of the step drivers (c8_krylov_solve in include/c8.h):
+// right-preconditioned BiCGStab on the four-block system as the drivers hold it, preconditioned with the inverse of
+// every node's own diagonal block (node-block Jacobi).  DESIGN.md section 13.
+//
+//   vectors   one flat array per vector: the u segment [nnodes * ND], then the p segment [nnodes] (two residuals); the
+//             matrix stays in its four CSR value arrays (layout of DESIGN.md section 3.2), nothing is re-interleaved
+//   residual  r = b - A x at the start, at every restart and on exit comes from k_true_residual (plain CSR order, see there)
+//   kernels   per iteration: k_prec (p update + M^-1 p) -> k_spmv (v = A phat, partials of rhat.v) -> k_reduce (alpha)
+//             -> k_prec (s = r - alpha v, M^-1 s) -> k_spmv (t = A shat, partials of t.s, t.t) -> k_reduce (omega)
+//             -> k_update (x, r, partials of rhat.r, r.r) -> k_reduce (rho, beta, |r|^2, stop flag, iteration count)
+//   scalars   alpha, omega, beta, rho live in device memory (KryScalars) and are read from there by the next kernel; the
+//             host copies the struct back every `check_every` iterations only
+//   sums      per-block partials in a fixed order, then one block adds the partials in a fixed order (the pattern of
+//             k_vfm_reduce): no floating-point atomics, a solve is a pure function of its inputs
+//   stop      once the recursive residual meets the tolerance (stop = 1) or a breakdown is seen (stop = 2) every later
+//             kernel of the batch returns at once: x and the iteration count stay those of that iteration
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <string>
+
+#include "../../include/c8.h"
+#include "c8_api_internal.hpp"
+
+static int fail(int code, std::string const& msg) { return c8_fail(code, msg); }
+#define C8_HIP(call)                                                                               \
+  do {                                                                                             \
+    hipError_t err__ = (call);                                                                     \
+    if (err__ != hipSuccess) return fail(C8_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(err__)); \
+  } while (0)
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int UPDATE_MAX_BLOCKS = 2048;  // grid of the elementwise kernel (grid-stride beyond)
+constexpr double BREAKDOWN = 1e-300;
+
+struct KryScalars {
+  double rho, alpha, omega, beta, rr;
+  int32_t stop;      // 0 running, 1 recursive residual within tolerance, 2 breakdown
+  int32_t iters;     // completed iterations
+  int32_t bad_node;  // set-up kernel: smallest node whose diagonal block cannot be inverted (INT_MAX: none)
+  int32_t pad;
+};
+
+struct Blocks {
+  double const *A00, *A01, *A10, *A11;
+};
+
+// the dispatcher deals workgroups round-robin over the 8 XCDs: XCD x takes the x-th contiguous eighth of the node order
+// in every kernel that walks the nodes, so that a node's rows, its inverse block and its neighbours' vector entries meet
+// in one L2 from kernel to kernel
+__device__ __forceinline__ int xcd_block(int b, int nblocks) {
+  int const chunk = (nblocks + 7) >> 3;
+  return (b & 7) * chunk + (b >> 3);
+}
+inline int xcd_grid(int nblocks) { return ((nblocks + 7) / 8) * 8; }
+
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.79769313486231570e308; }  // false for NaN
+
+// sum of a over the block in a fixed order (shuffle tree per wavefront, then the wavefronts in order); valid in thread 0
+__device__ __forceinline__ double block_sum(double a, double* sm) {
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o);
+  __syncthreads();  // sm may still be read from a previous call
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
+  __syncthreads();
+  double tot = 0.;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < TPB / 64; ++w) tot += sm[w];
+  return tot;
+}
+
+// ---- node-block Jacobi set-up: one work item per node gathers the node's own NB x NB block out of the four value
+// arrays (node's own position ks in its graph row) and inverts it by Gauss-Jordan with partial pivoting.  Every index
+// below is a compile-time constant after unrolling (row swaps are selects): the block stays in registers.
+template <int ND, int NRES>
+__global__ void __launch_bounds__(TPB) k_setup(int nn, int nblocks, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj,
+                                               Blocks A, double* __restrict__ minv, KryScalars* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * TPB + threadIdx.x;
+  if (node >= nn) return;
+  int64_t const np = nodeptr[node];
+  int const deg = (int)(nodeptr[node + 1] - np);
+  int ks = -1;
+  for (int k = 0; k < deg; ++k)
+    if (nodeadj[np + k] == node) ks = k;
+  double a[NB][NB], inv[NB][NB];
+  bool ok = ks >= 0;
+  if (ks < 0) ks = 0;
+#pragma unroll
+  for (int ri = 0; ri < NB; ++ri)
+#pragma unroll
+    for (int cj = 0; cj < NB; ++cj) {
+      int const i = ri < ND ? 0 : 1, eq = ri < ND ? ri : 0, j = cj < ND ? 0 : 1, e = cj < ND ? cj : 0;
+      int const ni = i ? 1 : ND, nj = j ? 1 : ND;
+      double const* vals = i ? (j ? A.A11 : A.A10) : (j ? A.A01 : A.A00);
+      a[ri][cj] = deg > 0 ? vals[np * ni * nj + (int64_t)eq * deg * nj + (int64_t)ks * nj + e] : 0.;
+      inv[ri][cj] = ri == cj ? 1. : 0.;
+    }
+#pragma unroll
+  for (int c = 0; c < NB; ++c) {
+#pragma unroll
+    for (int r = c + 1; r < NB; ++r) {  // after these selects row c holds the largest |entry| of column c
+      bool const sw = fabs(a[r][c]) > fabs(a[c][c]);
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        double const a0 = a[c][k], a1 = a[r][k], i0 = inv[c][k], i1 = inv[r][k];
+        a[c][k] = sw ? a1 : a0;
+        a[r][k] = sw ? a0 : a1;
+        inv[c][k] = sw ? i1 : i0;
+        inv[r][k] = sw ? i0 : i1;
+      }
+    }
+    double const piv = a[c][c];
+    if (piv == 0. || !finite_d(piv)) ok = false;
+    double const ip = 1. / piv;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      a[c][k] *= ip;
+      inv[c][k] *= ip;
+    }
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      if (r == c) continue;
+      double const f = a[r][c];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        a[r][k] -= f * a[c][k];
+        inv[r][k] -= f * inv[c][k];
+      }
+    }
+  }
+#pragma unroll
+  for (int ri = 0; ri < NB; ++ri)
+#pragma unroll
+    for (int cj = 0; cj < NB; ++cj) {
+      if (!finite_d(inv[ri][cj])) ok = false;
+      minv[(size_t)node * NB * NB + ri * NB + cj] = inv[ri][cj];
+    }
+  if (!ok) atomicMin(&S->bad_node, node);  // (integer) the smallest such node, whatever the order of the blocks
+}
+
+// ---- vector update fused with the preconditioner apply, one work item per node
+//   SECOND = 0:  p = r + beta (p - omega v),  out = M^-1 p      (p updated in place)
+//   SECOND = 1:  s = r - alpha v,             out = M^-1 s
+template <int ND, int NRES, int SECOND>
+__global__ void __launch_bounds__(TPB) k_prec(int nn, int nblocks, double const* __restrict__ minv, double const* __restrict__ r,
+                                              double const* __restrict__ v, double* __restrict__ w, double* __restrict__ out,
+                                              KryScalars const* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  if (S->stop) return;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * TPB + threadIdx.x;
+  if (node >= nn) return;
+  size_t const n0 = (size_t)nn * ND;
+  double const alpha = S->alpha, omega = S->omega, beta = S->beta;
+  double y[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    size_t const idx = k < ND ? (size_t)node * ND + k : n0 + node;
+    y[k] = SECOND ? r[idx] - alpha * v[idx] : r[idx] + beta * (w[idx] - omega * v[idx]);
+    w[idx] = y[k];
+  }
+  double const* m = minv + (size_t)node * NB * NB;
+#pragma unroll
+  for (int ri = 0; ri < NB; ++ri) {
+    double acc = 0.;
+#pragma unroll
+    for (int cj = 0; cj < NB; ++cj) acc += m[ri * NB + cj] * y[cj];
+    out[ri < ND ? (size_t)node * ND + ri : n0 + node] = acc;
+  }
+}
+
+// ---- y = A x over the four blocks, G lanes per node: lane l takes the neighbours l, l + G, ... of the node's graph row
+// and all NB rows of the node at once (consecutive lanes read consecutive ND-vectors of a CSR row), then a butterfly over
+// the G lanes.  The inner products the method needs of y leave as one partial per block.
+//   MODE 0:  v = A phat;      part[lb] = rhat . v                                   (y = v, a0 = rhat)
+//   MODE 1:  t = A shat;      part[lb] = t . s,  part[nblocks + lb] = t . t         (y = t, a0 = s)
+template <int ND, int NRES, int G, int MODE>
+__global__ void __launch_bounds__(TPB) k_spmv(int nn, int nblocks, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj,
+                                              Blocks A, double const* __restrict__ x, double* __restrict__ y, double const* __restrict__ a0,
+                                              double* __restrict__ part, KryScalars const* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  constexpr int NPB = TPB / G;
+  __shared__ double sm[TPB / 64];
+  if (S->stop) return;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * NPB + threadIdx.x / G, lane = threadIdx.x % G;
+  size_t const n0 = (size_t)nn * ND;
+  double acc[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) acc[k] = 0.;
+  if (node < nn) {
+    int64_t const np = nodeptr[node];
+    int const deg = (int)(nodeptr[node + 1] - np);
+    for (int k = lane; k < deg; k += G) {
+      int const cn = nodeadj[np + k];
+      double xv[NB];
+#pragma unroll
+      for (int e = 0; e < NB; ++e) xv[e] = x[e < ND ? (size_t)cn * ND + e : n0 + cn];
+#pragma unroll
+      for (int ri = 0; ri < ND; ++ri) {
+        double const* row = A.A00 + np * ND * ND + (int64_t)ri * deg * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[ri] += row[e] * xv[e];
+        if (NRES == 2) acc[ri] += A.A01[np * ND + (int64_t)ri * deg + k] * xv[NB - 1];
+      }
+      if (NRES == 2) {
+        double const* row = A.A10 + np * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[NB - 1] += row[e] * xv[e];
+        acc[NB - 1] += A.A11[np + k] * xv[NB - 1];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k)
+    for (int o = G / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, G);
+  double d0 = 0., d1 = 0.;
+  if (node < nn && lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      size_t const idx = k < ND ? (size_t)node * ND + k : n0 + node;
+      y[idx] = acc[k];
+      d0 += a0[idx] * acc[k];
+      if (MODE == 1) d1 += acc[k] * acc[k];
+    }
+  }
+  double const s0 = block_sum(d0, sm);
+  if (threadIdx.x == 0) part[lb] = s0;
+  if (MODE == 1) {
+    double const s1 = block_sum(d1, sm);
+    if (threadIdx.x == 0) part[nblocks + lb] = s1;
+  }
+}
+
+// ---- the TRUE residual: r = b - A x, rhat = r, p = v = 0, part[lb] = r . r -- the start, every restart, and the number a
+// solve reports and is judged by.  At the tolerance the residual is a difference of numbers 1 / rel_tol times larger, so
+// two summation orders of A x differ in |b - A x| by eps |A| |x| / |r|: 1e-6 to 3e-4 relative between the lane-parallel
+// sums of k_spmv and a host's row-by-row product on the test systems.  The reported value is therefore DEFINED by the
+// plain CSR order -- each row summed from zero over the columns of the u block, then of the p block, in the order of the
+// graphs, every product and sum rounded separately (no fused multiply-add) -- which is the order of a host recomputation
+// from the downloaded blocks (SciPy's csr_matvec), so that a caller can check the number and not only its magnitude.  One
+// work item per node; runs a few times per solve, not per iteration.
+template <int ND, int NRES>
+__global__ void __launch_bounds__(TPB) k_true_residual(int nn, int nblocks, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj,
+                                                       Blocks A, double const* __restrict__ x, double const* __restrict__ b0,
+                                                       double const* __restrict__ b1, double* __restrict__ r, double* __restrict__ rhat,
+                                                       double* __restrict__ p, double* __restrict__ v, double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double sm[TPB / 64];
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * TPB + threadIdx.x;
+  size_t const n0 = (size_t)nn * ND;
+  double d0 = 0.;
+  if (node < nn) {
+    int64_t const np = nodeptr[node];
+    int const deg = (int)(nodeptr[node + 1] - np);
+    for (int ri = 0; ri < ND + (NRES == 2 ? 1 : 0); ++ri) {
+      bool const prow = ri == ND;
+      double const* a0 = prow ? A.A10 + np * ND : A.A00 + np * ND * ND + (int64_t)ri * deg * ND;   // the row in the u-column block
+      double sum = 0.;
+      for (int k = 0; k < deg; ++k) {
+        int const cn = nodeadj[np + k];
+        for (int e = 0; e < ND; ++e) sum = sum + a0[(int64_t)k * ND + e] * x[(size_t)cn * ND + e];
+      }
+      if (NRES == 2) {
+        double const* a1 = prow ? A.A11 + np : A.A01 + np * ND + (int64_t)ri * deg;                // ... in the p-column block
+        for (int k = 0; k < deg; ++k) sum = sum + a1[k] * x[n0 + nodeadj[np + k]];
+      }
+      size_t const idx = prow ? n0 + node : (size_t)node * ND + ri;
+      double const rn = (prow ? b1[node] : b0[(size_t)node * ND + ri]) - sum;
+      r[idx] = rn;
+      rhat[idx] = rn;
+      p[idx] = 0.;
+      v[idx] = 0.;
+      d0 = d0 + rn * rn;
+    }
+  }
+  double const s0 = block_sum(d0, sm);
+  if (threadIdx.x == 0) part[lb] = s0;
+}
+
+// ---- x += alpha phat + omega shat,  r = s - omega t;  part[b] = rhat . r,  part[gridDim + b] = r . r
+__global__ void __launch_bounds__(TPB) k_update(size_t n, double* __restrict__ x, double* __restrict__ r, double const* __restrict__ s,
+                                                double const* __restrict__ t, double const* __restrict__ phat, double const* __restrict__ shat,
+                                                double const* __restrict__ rhat, double* __restrict__ part, KryScalars const* S) {
+  __shared__ double sm[TPB / 64];
+  if (S->stop) return;
+  double const alpha = S->alpha, omega = S->omega;
+  double d0 = 0., d1 = 0.;
+  for (size_t i = blockIdx.x * (size_t)TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * TPB) {
+    x[i] += alpha * phat[i] + omega * shat[i];
+    double const rn = s[i] - omega * t[i];
+    r[i] = rn;
+    d0 += rhat[i] * rn;
+    d1 += rn * rn;
+  }
+  double const s0 = block_sum(d0, sm);
+  double const s1 = block_sum(d1, sm);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s0;
+    part[gridDim.x + blockIdx.x] = s1;
+  }
+}
+
+// ---- one block adds the partials (thread t the blocks t, t + TPB, ... in order, then the fixed tree of block_sum) and
+// forms the scalars of the recurrence in device memory
+//   KIND 0: alpha = rho / (rhat . v)           KIND 1: omega = (t . s) / (t . t)
+//   KIND 2: |r|^2, iteration count, stop flag, beta = (rho' / rho) (alpha / omega), rho = rho'
+//   KIND 3: start / restart: rho = |r|^2 (rhat = r), beta = 0, alpha = omega = 1, stop = 0
+template <int KIND>
+__global__ void __launch_bounds__(TPB) k_reduce(double const* __restrict__ part, int nb, double tol2, KryScalars* S) {
+  __shared__ double sm[TPB / 64];
+  if (KIND != 3 && S->stop) return;
+  double a0 = 0., a1 = 0.;
+  for (int b = threadIdx.x; b < nb; b += TPB) a0 += part[b];
+  if (KIND == 1 || KIND == 2)
+    for (int b = threadIdx.x; b < nb; b += TPB) a1 += part[nb + b];
+  double const s0 = block_sum(a0, sm);
+  double const s1 = (KIND == 1 || KIND == 2) ? block_sum(a1, sm) : 0.;
+  if (threadIdx.x != 0) return;
+  if (KIND == 0) {
+    double const alpha = S->rho / s0;
+    if (!finite_d(alpha) || fabs(s0) < BREAKDOWN) S->stop = 2;
+    else S->alpha = alpha;
+  } else if (KIND == 1) {
+    double const omega = s0 / s1;
+    if (!finite_d(omega) || fabs(omega) < BREAKDOWN) S->stop = 2;
+    else S->omega = omega;
+  } else if (KIND == 2) {
+    S->rr = s1;
+    S->iters += 1;
+    if (s1 <= tol2) S->stop = 1;
+    else if (!finite_d(s1) || !finite_d(s0) || fabs(s0) < BREAKDOWN) S->stop = 2;
+    else {
+      S->beta = (s0 / S->rho) * (S->alpha / S->omega);
+      S->rho = s0;
+    }
+  } else {
+    S->rr = s0;
+    S->rho = s0;
+    S->beta = 0.;
+    S->alpha = 1.;
+    S->omega = 1.;
+    S->stop = 0;
+  }
+}
+
+template <class T>
+int grow(T** buf, size_t* have, size_t need) {
+  if (need <= *have) return C8_OK;
+  if (*buf) C8_HIP(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  C8_HIP(hipMalloc((void**)buf, need * sizeof(T)));
+  *have = need;
+  return C8_OK;
+}
+
+struct Solve {
+  c8_ctx* c;
+  int nn, nb_node, nb_spmv, nb_upd;
+  size_t n;  // length of a vector
+  Blocks A;
+  double const *b0, *b1;
+  double *x, *r, *rhat, *p, *v, *s, *t, *phat, *shat, *part, *minv;
+  KryScalars* S;
+  double tol2 = 0.;
+};
+
+template <int ND, int NRES>
+int launch_setup(Solve const& q) {
+  hipLaunchKernelGGL((k_setup<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, q.c->stream, q.nn, q.nb_node, q.c->d_nodeptr,
+                     q.c->d_nodeadj, q.A, q.minv, q.S);
+  C8_HIP(hipGetLastError());
+  return C8_OK;
+}
+
+// r = b - A x, rhat = r, p = v = 0 and the scalars of a fresh recurrence; S->rr = |b - A x|^2
+template <int ND, int NRES>
+int launch_residual(Solve const& q) {
+  hipLaunchKernelGGL((k_true_residual<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, q.c->stream, q.nn, q.nb_node, q.c->d_nodeptr,
+                     q.c->d_nodeadj, q.A, q.x, q.b0, q.b1, q.r, q.rhat, q.p, q.v, q.part);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<3>), dim3(1), dim3(TPB), 0, q.c->stream, q.part, q.nb_node, 0., q.S);
+  C8_HIP(hipGetLastError());
+  return C8_OK;
+}
+
+template <int ND, int NRES, int G>
+int launch_iteration(Solve const& q) {
+  hipStream_t const st = q.c->stream;
+  int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
+  hipLaunchKernelGGL((k_prec<ND, NRES, 0>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, q.nn, q.nb_node, q.minv, q.r, q.v, q.p, q.phat, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<0>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_prec<ND, NRES, 1>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, q.nn, q.nb_node, q.minv, q.r, q.v, q.s, q.shat, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<1>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_update, dim3(q.nb_upd), dim3(TPB), 0, st, q.n, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<2>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_upd, q.tol2, q.S);
+  C8_HIP(hipGetLastError());
+  return C8_OK;
+}
+
+struct Launchers {
+  int (*setup)(Solve const&);
+  int (*residual)(Solve const&);
+  int (*iteration)(Solve const&);
+  int group;
+};
+template <int ND, int NRES, int G>
+Launchers launchers() { return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>, launch_iteration<ND, NRES, G>, G}; }
+
+int read_scalars(Solve const& q, KryScalars* h) {
+  C8_HIP(hipMemcpyAsync(h, q.S, sizeof(KryScalars), hipMemcpyDeviceToHost, q.c->stream));
+  C8_HIP(hipStreamSynchronize(q.c->stream));
+  return C8_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info);
+int c8_krylov_solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info) {
+  int const rc = solve(c, sys, dx, opts, info);
+  if (info) info->status = rc;  // whatever path returned: argument, device and unsupported errors included
+  return rc;
+}
+static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info) {
+  if (info) *info = c8_krylov_info{0, 0, C8_ERR_ARG, 0., 0.};
+  if (!c || !sys || !dx) return fail(C8_ERR_ARG, "c8_krylov_solve: null argument");
+  bool const two = c->nres == 2;
+  if (!sys->A[0][0] || !sys->b[0] || !dx[0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1] || !sys->b[1] || !dx[1])))
+    return fail(C8_ERR_ARG, "c8_krylov_solve: null array in the system or in dx");
+  if (c->halo) {
+    if (info) info->status = C8_ERR_UNSUPPORTED;
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: a halo is attached to the context; the multi-part solve (halo exchange inside A x, "
+                                    "inner products summed over the parts) is not implemented");
+  }
+  int const max_iters = (opts && opts->max_iters > 0) ? opts->max_iters : 20000;
+  int const check_every = (opts && opts->check_every > 0) ? opts->check_every : 10;
+  int const max_restarts = (opts && opts->max_restarts > 0) ? opts->max_restarts : 5;
+  double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
+  double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
+
+  Launchers L;
+  if (c->ndims == 3 && two) L = launchers<3, 2, 16>();
+  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>();
+  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>();
+  else {
+    if (info) info->status = C8_ERR_UNSUPPORTED;
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: no kernels for this number of dimensions and residuals");
+  }
+  int const nb = c->ndims + (two ? 1 : 0);
+
+  Solve q{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  size_t const n0 = (size_t)q.nn * c->ndims;
+  q.n = n0 + (two ? (size_t)q.nn : 0);
+  q.nb_node = (q.nn + TPB - 1) / TPB;
+  q.nb_spmv = (q.nn + TPB / L.group - 1) / (TPB / L.group);
+  q.nb_upd = (int)std::min<size_t>((q.n + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
+  if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve: empty mesh");
+  int rc;
+  if ((rc = grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * nb * nb)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_part, &c->kry_part_n, 2 * (size_t)std::max(q.nb_spmv, q.nb_upd))) != C8_OK) return rc;
+  if (!c->d_kry_scalars) C8_HIP(hipMalloc(&c->d_kry_scalars, sizeof(KryScalars)));
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  q.b0 = sys->b[0];
+  q.b1 = sys->b[1];
+  double* vec = c->d_kry_vec;
+  q.x = vec, q.r = vec + q.n, q.rhat = vec + 2 * q.n, q.p = vec + 3 * q.n, q.v = vec + 4 * q.n, q.s = vec + 5 * q.n;
+  q.t = vec + 6 * q.n, q.phat = vec + 7 * q.n, q.shat = vec + 8 * q.n;
+  q.part = c->d_kry_part;
+  q.minv = c->d_kry_minv;
+  q.S = (KryScalars*)c->d_kry_scalars;
+
+  // set-up: the inverses of the diagonal blocks, x = 0, r = rhat = b
+  KryScalars h{};
+  h.bad_node = INT_MAX;
+  C8_HIP(hipMemcpyAsync(q.S, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+  C8_HIP(hipMemsetAsync(q.x, 0, q.n * sizeof(double), c->stream));
+  if ((rc = L.setup(q)) != C8_OK) return rc;
+  if ((rc = L.residual(q)) != C8_OK) return rc;
+  if ((rc = read_scalars(q, &h)) != C8_OK) return rc;
+  if (h.bad_node != INT_MAX)
+    return fail(C8_ERR_ARG, "c8_krylov_solve: the diagonal block of node " + std::to_string(h.bad_node) +
+                            " is singular or not finite (node-block Jacobi preconditioner)");
+  double const b_norm = std::sqrt(h.rr);
+  if (!std::isfinite(b_norm)) return fail(C8_ERR_ARG, "c8_krylov_solve: the right-hand side or the matrix is not finite");
+  auto store = [&]() -> int {  // the iterate to the caller's arrays
+    C8_HIP(hipMemcpyAsync(dx[0], q.x, n0 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (two) C8_HIP(hipMemcpyAsync(dx[1], q.x + n0, (size_t)q.nn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return C8_OK;
+  };
+  if (b_norm == 0.) {
+    if (info) *info = c8_krylov_info{0, 0, C8_OK, 0., 0.};
+    return store();
+  }
+  double const tol = std::max(rel_tol * b_norm, abs_tol);
+  q.tol2 = tol * tol;
+
+  int restarts = 0, status = C8_NOT_CONVERGED;
+  double true_norm = b_norm;
+  while (true) {
+    int const batch = std::min(check_every, max_iters - h.iters);
+    for (int k = 0; k < batch; ++k)
+      if ((rc = L.iteration(q)) != C8_OK) return rc;
+    if ((rc = read_scalars(q, &h)) != C8_OK) return rc;
+    if (h.stop == 0 && h.iters < max_iters) continue;
+    // the recursive residual met the tolerance, the recurrence broke down, or the budget is spent: the TRUE residual
+    // decides (this also resets the recurrence at the current iterate: r = b - A x, rhat = r)
+    int const iters = h.iters;
+    if ((rc = L.residual(q)) != C8_OK) return rc;
+    if ((rc = read_scalars(q, &h)) != C8_OK) return rc;
+    true_norm = std::sqrt(h.rr);
+    if (true_norm <= tol) { status = C8_OK; break; }
+    if (iters >= max_iters || restarts >= max_restarts || !std::isfinite(true_norm)) break;
+    restarts++;
+  }
+  if (info) *info = c8_krylov_info{h.iters, restarts, status, b_norm, true_norm};
+  if ((rc = store()) != C8_OK) return rc;
+  if (status != C8_OK)
+    return fail(C8_NOT_CONVERGED, "c8_krylov_solve: |b - A x| / |b| = " + std::to_string(true_norm / b_norm) + " after " +
+                                  std::to_string(h.iters) + " iterations and " + std::to_string(restarts) + " restarts");
+  return C8_OK;
+}
+
+int c8_krylov_linear_solve(void* user, const c8_system* sys, double* const dx[2]) {
+  c8_krylov_user* u = (c8_krylov_user*)user;
+  if (!u || !u->ctx) return fail(C8_ERR_ARG, "c8_krylov_linear_solve: user must point to a c8_krylov_user with its ctx set");
+  int const rc = c8_krylov_solve(u->ctx, sys, dx, &u->opts, &u->info);
+  u->total_iters += u->info.iters;
+  u->solves += 1;
+  return rc;
+}
+
+}  // extern "C"

@@ -100,6 +100,21 @@ class System(C.Structure):
     _fields_ = [("A", (C.c_void_p * 2) * 2), ("b", C.c_void_p * 2)]
 
 
+class KrylovOpts(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("check_every", C.c_int32), ("max_restarts", C.c_int32),
+                ("rel_tol", C.c_double), ("abs_tol", C.c_double)]
+
+
+class KrylovInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("restarts", C.c_int32), ("status", C.c_int32), ("b_norm", C.c_double),
+                ("residual_norm", C.c_double)]
+
+
+class KrylovUser(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("opts", KrylovOpts), ("info", KrylovInfo), ("total_iters", C.c_int64),
+                ("solves", C.c_int64)]
+
+
 LINEAR_SOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p))
 
 # every symbol include/c8.h declares: (name, restype, argtypes)
@@ -161,6 +176,8 @@ SYMBOLS = [
                                        C.POINTER(Tbc), C.POINTER(NewtonOpts), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("c8_adjoint_solve_step", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(System), C.c_int, C.POINTER(Dbc), C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("c8_krylov_solve", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p), C.POINTER(KrylovOpts), C.POINTER(KrylovInfo)]),
+    ("c8_krylov_linear_solve", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p)]),
     ("c8_transform_params", C.c_int, [C.c_int, dp, i32p, dp, dp, C.c_int, dp]),
     ("c8_transform_gradient", C.c_int, [C.c_int, dp, dp, i32p, dp, dp, dp]),
     ("c8_brick_mesh", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, i32p]),

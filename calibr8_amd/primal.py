@@ -2,7 +2,8 @@
 
 Each load step calls `c8_primal_solve_step` (C++ Newton + line search around the HIP assembly, boundary
 conditions applied on the device).  The sparse linear solve is the caller's callback -- the reference
-uses Belos/Teko/MueLu, out of scope here; `scipy_solver` below is the direct solve the tests use.
+uses Belos/Teko/MueLu, out of scope here; `scipy_solver` below is the direct solve on the host (the default),
+`device_solver` the library's own preconditioned BiCGStab, which keeps the system on the device.
 """
 import ctypes as C
 
@@ -39,6 +40,45 @@ def scipy_solver(asm):
         return 0
 
     return _l.LINEAR_SOLVE_FN(solve)
+
+
+class DeviceSolver:
+    """`c8_krylov_linear_solve` with its `c8_krylov_user` block: the step drivers call the library's BiCGStab straight
+    from C++, the system never leaves the device.  `last` is the c8_krylov_info of the last solve."""
+
+    def __init__(self, asm, rel_tol=1e-10, max_iters=20000, check_every=10, max_restarts=5, abs_tol=0.0):
+        self.asm = asm  # the context must outlive the callback block
+        self.user = _l.KrylovUser()
+        self.user.ctx = asm.h.value
+        self.user.opts = _l.KrylovOpts(int(max_iters), int(check_every), int(max_restarts), float(rel_tol), float(abs_tol))
+        self.fn = C.cast(asm.L.c8_krylov_linear_solve, C.c_void_p)
+
+    @property
+    def last(self):
+        i = self.user.info
+        return _l.KrylovInfo(i.iters, i.restarts, i.status, i.b_norm, i.residual_norm)
+
+    @property
+    def total_iters(self):
+        return int(self.user.total_iters)
+
+    @property
+    def solves(self):
+        return int(self.user.solves)
+
+
+def device_solver(asm, rel_tol=1e-10, max_iters=20000, **opts):
+    """Linear solve on the device: right-preconditioned BiCGStab with node-block Jacobi (c8_krylov_solve).  Usable wherever
+    `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem, FEMUProblem.
+    opts: check_every, max_restarts, abs_tol (c8_krylov_opts).  One part only: a context with a halo is refused."""
+    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, **opts)
+
+
+def _callback(solver):
+    """(function pointer, user pointer) of a linear solver for the step drivers"""
+    if isinstance(solver, DeviceSolver):
+        return solver.fn, C.c_void_p(C.addressof(solver.user))
+    return C.cast(solver, C.c_void_p), None
 
 
 def distributed_scipy_solver(asm, plan, dist):
@@ -183,8 +223,9 @@ class PrimalDriver:
         sy = self.ls.c_struct()
         d, tb, keep = self._bc_structs(step * self.step_size)
         iters = C.c_int32(0)
+        fn, user = _callback(self.solver)
         rc = asm.L.c8_primal_solve_step(asm.h, C.byref(st), C.byref(sy), len(self.dbcs), d, len(self.tbcs), tb,
-                                        C.byref(self.opts), C.cast(self.solver, C.c_void_p), None, C.byref(iters))
+                                        C.byref(self.opts), fn, user, C.byref(iters))
         _l.check(rc)
         self.newton_iters.append(iters.value)
         self.u.append(u)
@@ -232,13 +273,14 @@ def adjoint_gradient(primal, nparams):
     d = (_l.Dbc * max(1, len(primal.dbcs)))()
     for k, (resid, eq, nodes, _) in enumerate(primal.dbcs):
         d[k] = _l.Dbc(resid, eq, len(nodes), primal._dbc_nodes[k].data_ptr(), zero_vals[k].data_ptr())
+    fn, user = _callback(primal.solver)
     for step in range(nsteps, 0, -1):
         primal.begin_qoi_step(step)
         st = asm._state(primal.u[step], primal.p[step], primal.u[step - 1], primal.p[step - 1], primal.xi[step - 1],
                         primal.xi[step])
         z = (C.c_void_p * 2)(z_u.data_ptr(), z_p.data_ptr())
         rc = asm.L.c8_adjoint_solve_step(asm.h, C.byref(st), C.byref(sy), len(primal.dbcs), d,
-                                         C.cast(primal.solver, C.c_void_p), None, z, C.c_void_p(phi.data_ptr()),
+                                         fn, user, z, C.c_void_p(phi.data_ptr()),
                                          C.c_void_p(g.data_ptr()), C.c_void_p(f.data_ptr()), C.c_void_p(grad.data_ptr()))
         _l.check(rc)
     torch.cuda.synchronize()

@@ -365,6 +365,43 @@ int c8_adjoint_solve_step(c8_ctx* ctx, const c8_state* st, const c8_system* sys,
                           c8_linear_solve_fn solve, void* user, double* const z[2], double* phi, double* g, double* f,
                           double* grad);
 
+/* ---- device-resident linear solve for the step drivers -----------------------------------------------------
+ * Right-preconditioned BiCGStab on the system as the drivers hold it (the four CSR value arrays over the context's
+ * graphs, or A[0][0] / b[0] alone when c8_num_residuals() == 1), preconditioned with the inverse of every node's own
+ * diagonal block over its equations (u and p of the node: 4 x 4, 3 x 3 on tri3 meshes, 2 x 2 under
+ * mechanics_plane_stress).  Everything stays in HBM on the context's stream; the host reads the residual norm every
+ * `check_every` iterations.  No floating-point atomics: the same inputs give the same bits.  This stands in for the
+ * reference's Belos / Teko / MueLu stack on one part; it is no multigrid (iteration counts grow like 1 / h). */
+typedef struct {
+  int32_t max_iters;      /* iterations (two A x each); default 20000 when <= 0 */
+  int32_t check_every;    /* host reads the residual norm every this many iterations; default 10 */
+  int32_t max_restarts;   /* restarts of the recurrence from the current iterate, after a breakdown or after a recursive
+                             residual that met the tolerance while the true residual did not (one budget); default 5 */
+  double rel_tol;         /* ||b - A x|| <= rel_tol ||b||; default 1e-10 */
+  double abs_tol;         /* or <= abs_tol; default 0 */
+} c8_krylov_opts;
+typedef struct {
+  int32_t iters, restarts, status;  /* status = the return value of the solve */
+  double b_norm, residual_norm;     /* residual_norm = ||b - A x||, recomputed from x on exit */
+} c8_krylov_info;
+/* dx (DEVICE pointers, as b) is overwritten; the start vector is 0.  opts NULL (or a field <= 0) = the defaults; info
+ * may be NULL.  Returns C8_OK; C8_NOT_CONVERGED with dx holding the last iterate and info filled; C8_ERR_ARG for null
+ * pointers, a right-hand side that is not finite, or a node whose diagonal block is singular or not finite (the
+ * message of c8_last_error names the node; nothing is iterated); C8_ERR_UNSUPPORTED when a halo is attached to the
+ * context: a multi-part solve needs the halo exchange inside A x and inner products summed over the parts, which this
+ * solver does not have.  b = 0 returns dx = 0 after 0 iterations. */
+int c8_krylov_solve(c8_ctx* ctx, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts,
+                    c8_krylov_info* info);
+/* The same as a c8_linear_solve_fn for c8_primal_solve_step / c8_adjoint_solve_step: `user` points to a
+ * c8_krylov_user; `info` receives the last solve, `total_iters` and `solves` add up over the calls. */
+typedef struct {
+  c8_ctx* ctx;
+  c8_krylov_opts opts;
+  c8_krylov_info info;
+  int64_t total_iters, solves;
+} c8_krylov_user;
+int c8_krylov_linear_solve(void* user, const c8_system* sys, double* const dx[2]);
+
 /* ---- multi-part meshes: owned/ghost halo and reductions ---------------------------------
  * One process per GPU, one mesh part per process, elements not ghosted, nodes on part boundaries shared -- the
  * reference's MPI scheme (disc.cpp:237,297).  Local node numbering of a part: OWNED nodes, then GHOST nodes (touched

@@ -1,7 +1,8 @@
-"""Print VGPR / scratch / occupancy / LDS of every kernel in c8_kernels.hip (hipcc resource-usage remarks)."""
+"""Print VGPR / scratch / occupancy / LDS of every kernel in c8_kernels.hip (hipcc resource-usage remarks).
+C8_SRC=<file under calibr8_amd/csrc> names another translation unit, e.g. C8_SRC=c8_krylov.hip."""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "calibr8_amd", "csrc", "c8_kernels.hip")
+src = os.path.join(root, "calibr8_amd", "csrc", os.environ.get("C8_SRC", "c8_kernels.hip"))
 cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
        "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + sys.argv[2:]
 t = subprocess.run(cmd, capture_output=True, text=True).stderr
