@@ -100,6 +100,12 @@ struct c8_ctx {
   double* d_kry_part = nullptr;      // per-block partial sums of the inner products
   void* d_kry_scalars = nullptr;     // rho, alpha, omega, beta, |r|^2, stop flag, iteration count (+ the set-up kernel's flag)
   size_t kry_minv_n = 0, kry_vec_n = 0, kry_part_n = 0;
+  // ... over parts (c8_krylov_solve_parts): the owned nodes without / with a ghost or phantom column, interior first
+  std::vector<int32_t> kry_list;
+  int kry_list_owned = -1;           // num_owned the lists were built for (-1: not built)
+  int kry_n_interior = 0;
+  int32_t* d_kry_list = nullptr;
+  double* d_kry_sums = nullptr;      // the local sums of an inner product, all-reduced in place
 };
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
 int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);
@@ -114,3 +120,13 @@ int c8_qoi_postprocess(c8_ctx* c, double* J);
 int c8_parts_allreduce(c8_ctx* c, double* values, int n);  // SUM over the parts: caller's callback, else the halo's communicator; no-op on one part
 int c8_halo_num_owned(c8_halo const* h);
 void c8_halo_detach_ctx(c8_ctx* c);  // c8_destroy: the halo attached to c (if any) forgets the context and its communicator
+// ... for the multi-part Krylov solve (c8_krylov.hip).  `degraded`: this rank has met a device error and only keeps the
+// collective sequence of the other ranks going (host transport: the callbacks are entered with the host buffers, NaN in an
+// all-reduce; no device work); its return values are then meaningless.
+int c8_halo_rank(c8_halo const* h);
+int c8_halo_num_ranks(c8_halo const* h);
+c8_comm* c8_halo_comm(c8_halo const* h);
+int c8_halo_import_start(c8_halo* h, double* v0, double* v1, bool degraded);   // C3 of the vector {v0, v1}: pack and send
+int c8_halo_import_finish(c8_halo* h, double* v0, double* v1, bool degraded);  // ... store what arrived in the copies
+// in-place SUM over the ranks of n <= 64 doubles in DEVICE memory, ordered after and before the work on `stream`
+int c8_comm_allreduce_device(c8_comm* cm, hipStream_t stream, double* d_values, int n, bool degraded);

@@ -21,6 +21,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -143,6 +144,8 @@ struct c8_comm {
   ncclComm_t nccl = nullptr;
   hipStream_t stream = nullptr;          // RCCL transport: the stream the messages travel on
   double* d_small = nullptr;             // device scratch of the small all-reduce
+  double* h_small = nullptr;             // host transport: pinned staging of the device-buffer all-reduce (at its first use)
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;  // RCCL transport: order the device-buffer all-reduce against the caller's stream
   c8_host_exchange_fn host_exchange = nullptr;
   c8_host_allreduce_fn host_allreduce = nullptr;
   void* user = nullptr;
@@ -273,6 +276,63 @@ int c8_parts_allreduce(c8_ctx* c, double* values, int n) {
   return C8_OK;
 }
 int c8_halo_num_owned(c8_halo const* h) { return h->nowned; }
+int c8_halo_rank(c8_halo const* h) { return h->rank; }
+int c8_halo_num_ranks(c8_halo const* h) { return h->nranks; }
+c8_comm* c8_halo_comm(c8_halo const* h) { return h->comm; }
+
+// C3 of one vector of the Krylov solve in two halves, so that the rows without a copy's column are multiplied meanwhile
+int c8_halo_import_start(c8_halo* h, double* v0, double* v1, bool degraded) {
+  if (degraded) {  // keep the other ranks' collective going: the callback with the host buffers as they are
+    c8_comm* cm = h->comm;
+    h->pending = nullptr;
+    if (!cm->nccl) (void)cm->host_exchange(cm->user, h->h_sendbuf, h->import.send_counts.data(), h->h_recvbuf, h->import.recv_counts.data());
+    return C8_ERR_DEVICE;
+  }
+  int const rc = start_exchange(h, h->import, Segs{{nullptr, nullptr, nullptr, nullptr, v0, v1}});
+  // host transport: a device error comes before the callback, which the other ranks are waiting in
+  if (rc == C8_ERR_DEVICE && !h->comm->nccl) {
+    std::string const msg = c8_last_error();
+    (void)c8_halo_import_start(h, v0, v1, true);
+    return c8_fail(C8_ERR_DEVICE, msg);
+  }
+  return rc;
+}
+int c8_halo_import_finish(c8_halo* h, double* v0, double* v1, bool degraded) {
+  if (degraded) { h->pending = nullptr; return C8_ERR_DEVICE; }
+  return finish_exchange(h, Segs{{nullptr, nullptr, nullptr, nullptr, v0, v1}});
+}
+
+// RCCL: ncclAllReduce in place on the communicator's stream, between two events: the host does not wait.  Host transport:
+// copy down, the callback, copy up (one rank: nothing to add).
+int c8_comm_allreduce_device(c8_comm* cm, hipStream_t stream, double* d_values, int n, bool degraded) {
+  if (!cm || !d_values || n < 1 || n > 64) return c8_fail(C8_ERR_ARG, "c8_comm_allreduce_device: bad argument");
+  if (cm->nccl) {
+    if (degraded) return C8_ERR_DEVICE;  // a device in error cannot enqueue the collective; the other ranks end with RCCL's own error
+    C8H_HIP(hipEventRecord(cm->ev_in, stream));
+    C8H_HIP(hipStreamWaitEvent(cm->stream, cm->ev_in, 0));
+    C8H_NCCL(rccl().AllReduce(d_values, d_values, (size_t)n, ncclDouble, ncclSum, cm->nccl, cm->stream));
+    C8H_HIP(hipEventRecord(cm->ev_out, cm->stream));
+    C8H_HIP(hipStreamWaitEvent(stream, cm->ev_out, 0));
+    return C8_OK;
+  }
+  if (cm->nranks == 1) return C8_OK;
+  hipError_t err = hipSuccess;
+  if (!degraded) {
+    if (!cm->h_small) err = hipHostMalloc((void**)&cm->h_small, 64 * sizeof(double), hipHostMallocDefault);
+    if (err == hipSuccess) err = hipMemcpyAsync(cm->h_small, d_values, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+  }
+  if (degraded || err != hipSuccess) {  // the other ranks are waiting in the callback: enter it, with a value that stops them
+    double nan[64];
+    for (int k = 0; k < n; ++k) nan[k] = std::nan("");  // every rank's scalars turn NaN: the recurrence stops everywhere
+    (void)cm->host_allreduce(cm->user, nan, n);
+    return degraded ? C8_ERR_DEVICE : c8_fail(C8_ERR_DEVICE, std::string("c8_comm_allreduce_device: ") + hipGetErrorString(err));
+  }
+  if (cm->host_allreduce(cm->user, cm->h_small, n) != 0) return c8_fail(C8_ERR_ARG, "c8_comm_allreduce_device: the host all-reduce callback failed");
+  // the next copy down is ordered after this copy up on `stream`, and the host writes h_small only after it
+  C8H_HIP(hipMemcpyAsync(d_values, cm->h_small, n * sizeof(double), hipMemcpyHostToDevice, stream));
+  return C8_OK;
+}
 void c8_halo_detach_ctx(c8_ctx* c) {
   c8_halo* h = c->halo;
   if (!h) return;
@@ -313,7 +373,8 @@ int c8_comm_create_rccl(const void* id_in, int rank, int nranks, c8_comm** out) 
     delete cm;
     return c8_fail(C8_ERR_DEVICE, std::string("c8_comm_create_rccl: ncclCommInitRank: ") + R.GetErrorString(res));
   }
-  if (hipStreamCreateWithFlags(&cm->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&cm->d_small, 64 * sizeof(double)) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&cm->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&cm->d_small, 64 * sizeof(double)) != hipSuccess ||
+      hipEventCreateWithFlags(&cm->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&cm->ev_out, hipEventDisableTiming) != hipSuccess) {
     c8_comm_destroy(cm);
     return c8_fail(C8_ERR_DEVICE, "c8_comm_create_rccl: stream / scratch allocation failed");
   }
@@ -338,6 +399,9 @@ void c8_comm_destroy(c8_comm* cm) {
   if (cm->nccl) (void)rccl().CommDestroy(cm->nccl);
   if (cm->stream) (void)hipStreamDestroy(cm->stream);
   (void)hipFree(cm->d_small);
+  if (cm->h_small) (void)hipHostFree(cm->h_small);
+  if (cm->ev_in) (void)hipEventDestroy(cm->ev_in);
+  if (cm->ev_out) (void)hipEventDestroy(cm->ev_out);
   delete cm;
 }
 int c8_comm_rank(const c8_comm* cm) { return cm ? cm->rank : C8_ERR_ARG; }

@@ -14,12 +14,23 @@
 //             k_vfm_reduce): no floating-point atomics, a solve is a pure function of its inputs
 //   stop      once the recursive residual meets the tolerance (stop = 1) or a breakdown is seen (stop = 2) every later
 //             kernel of the batch returns at once: x and the iteration count stay those of that iteration
+//
+// Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
+// the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
+// entries are addressable and the halo's import tables apply to {v, v + nnodes * ND}; every kernel runs over the OWNED
+// nodes only.  A x: start the import of phat (shat), multiply the owned rows that have only owned columns (the interior
+// list), finish the import, multiply the other owned rows (the boundary list).  An inner product: per-block partials in
+// fixed slots (interior blocks, then boundary blocks) -> k_sums (one block, the local sums) -> one all-reduce of the 1-2
+// doubles over the communicator -> k_scalars (alpha / omega / rho, beta, |r|^2, stop flag from the GLOBAL sums, in device
+// memory).  THREE ALL-REDUCES AND TWO IMPORTS PER ITERATION.  Every scalar and the stop flag derive from all-reduced
+// values only; at every host read the ranks all-reduce (iterations, stop flag, failure marker) and leave together.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <string>
+#include <vector>
 
 #include "../../include/c8.h"
 #include "c8_api_internal.hpp"
@@ -435,6 +446,358 @@ int read_scalars(Solve const& q, KryScalars* h) {
   return C8_OK;
 }
 
+// ======================================================================================================================
+// The kernels of the multi-part solve.  nown = owned nodes (the rows this part iterates on), nn = local nodes (owned,
+// ghost, phantom: the p segment of a vector starts at nn * ND).  Nothing in a ghost or phantom entry enters a sum.
+// ======================================================================================================================
+
+// k_prec over the owned nodes
+template <int ND, int NRES, int SECOND>
+__global__ void __launch_bounds__(TPB) k_prec_own(int nown, int nn, int nblocks, double const* __restrict__ minv, double const* __restrict__ r,
+                                                  double const* __restrict__ v, double* __restrict__ w, double* __restrict__ out,
+                                                  KryScalars const* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  if (S->stop) return;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * TPB + threadIdx.x;
+  if (node >= nown) return;
+  size_t const n0 = (size_t)nn * ND;
+  double const alpha = S->alpha, omega = S->omega, beta = S->beta;
+  double y[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    size_t const idx = k < ND ? (size_t)node * ND + k : n0 + node;
+    y[k] = SECOND ? r[idx] - alpha * v[idx] : r[idx] + beta * (w[idx] - omega * v[idx]);
+    w[idx] = y[k];
+  }
+  double const* m = minv + (size_t)node * NB * NB;
+#pragma unroll
+  for (int ri = 0; ri < NB; ++ri) {
+    double acc = 0.;
+#pragma unroll
+    for (int cj = 0; cj < NB; ++cj) acc += m[ri * NB + cj] * y[cj];
+    out[ri < ND ? (size_t)node * ND + ri : n0 + node] = acc;
+  }
+}
+
+// k_spmv with the row taken from a node list (same lane mapping: G lanes per node): block lb of this launch multiplies
+// the nodes list[lb * NPB ...] and leaves its partials in slot slot0 + lb (and nslots + slot0 + lb) of `part`
+template <int ND, int NRES, int G, int MODE>
+__global__ void __launch_bounds__(TPB) k_spmv_list(int32_t const* __restrict__ list, int nlist, int nn, int nblocks, int slot0, int nslots,
+                                                   int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj, Blocks A,
+                                                   double const* __restrict__ x, double* __restrict__ y, double const* __restrict__ a0,
+                                                   double* __restrict__ part, KryScalars const* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  constexpr int NPB = TPB / G;
+  __shared__ double sm[TPB / 64];
+  if (S->stop) return;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const li = lb * NPB + threadIdx.x / G, lane = threadIdx.x % G;
+  bool const live = li < nlist;
+  int const node = live ? list[li] : 0;
+  size_t const n0 = (size_t)nn * ND;
+  double acc[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) acc[k] = 0.;
+  if (live) {
+    int64_t const np = nodeptr[node];
+    int const deg = (int)(nodeptr[node + 1] - np);
+    for (int k = lane; k < deg; k += G) {
+      int const cn = nodeadj[np + k];
+      double xv[NB];
+#pragma unroll
+      for (int e = 0; e < NB; ++e) xv[e] = x[e < ND ? (size_t)cn * ND + e : n0 + cn];
+#pragma unroll
+      for (int ri = 0; ri < ND; ++ri) {
+        double const* row = A.A00 + np * ND * ND + (int64_t)ri * deg * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[ri] += row[e] * xv[e];
+        if (NRES == 2) acc[ri] += A.A01[np * ND + (int64_t)ri * deg + k] * xv[NB - 1];
+      }
+      if (NRES == 2) {
+        double const* row = A.A10 + np * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[NB - 1] += row[e] * xv[e];
+        acc[NB - 1] += A.A11[np + k] * xv[NB - 1];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k)
+    for (int o = G / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, G);
+  double d0 = 0., d1 = 0.;
+  if (live && lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      size_t const idx = k < ND ? (size_t)node * ND + k : n0 + node;
+      y[idx] = acc[k];
+      d0 += a0[idx] * acc[k];
+      if (MODE == 1) d1 += acc[k] * acc[k];
+    }
+  }
+  double const s0 = block_sum(d0, sm);
+  if (threadIdx.x == 0) part[slot0 + lb] = s0;
+  if (MODE == 1) {
+    double const s1 = block_sum(d1, sm);
+    if (threadIdx.x == 0) part[nslots + slot0 + lb] = s1;
+  }
+}
+
+// k_true_residual over the owned rows, in the same plain CSR order: a row's value equals a host recomputation from the
+// gathered global matrix (x holds the owners' values in its ghost and phantom entries: imported before the launch)
+template <int ND, int NRES>
+__global__ void __launch_bounds__(TPB) k_true_residual_own(int nown, int nn, int nblocks, int32_t const* __restrict__ nodeptr,
+                                                           int32_t const* __restrict__ nodeadj, Blocks A, double const* __restrict__ x,
+                                                           double const* __restrict__ b0, double const* __restrict__ b1, double* __restrict__ r,
+                                                           double* __restrict__ rhat, double* __restrict__ p, double* __restrict__ v,
+                                                           double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double sm[TPB / 64];
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const node = lb * TPB + threadIdx.x;
+  size_t const n0 = (size_t)nn * ND;
+  double d0 = 0.;
+  if (node < nown) {
+    int64_t const np = nodeptr[node];
+    int const deg = (int)(nodeptr[node + 1] - np);
+    for (int ri = 0; ri < ND + (NRES == 2 ? 1 : 0); ++ri) {
+      bool const prow = ri == ND;
+      double const* a0 = prow ? A.A10 + np * ND : A.A00 + np * ND * ND + (int64_t)ri * deg * ND;
+      double sum = 0.;
+      for (int k = 0; k < deg; ++k) {
+        int const cn = nodeadj[np + k];
+        for (int e = 0; e < ND; ++e) sum = sum + a0[(int64_t)k * ND + e] * x[(size_t)cn * ND + e];
+      }
+      if (NRES == 2) {
+        double const* a1 = prow ? A.A11 + np : A.A01 + np * ND + (int64_t)ri * deg;
+        for (int k = 0; k < deg; ++k) sum = sum + a1[k] * x[n0 + nodeadj[np + k]];
+      }
+      size_t const idx = prow ? n0 + node : (size_t)node * ND + ri;
+      double const rn = (prow ? b1[node] : b0[(size_t)node * ND + ri]) - sum;
+      r[idx] = rn;
+      rhat[idx] = rn;
+      p[idx] = 0.;
+      v[idx] = 0.;
+      d0 = d0 + rn * rn;
+    }
+  }
+  double const s0 = block_sum(d0, sm);
+  if (threadIdx.x == 0) part[lb] = s0;
+}
+
+// k_update over the two owned ranges: [0, nu) of the u segment and [0, np_) of the p segment (which starts at n0)
+__global__ void __launch_bounds__(TPB) k_update_own(size_t nu, size_t np_, size_t n0, double* __restrict__ x, double* __restrict__ r,
+                                                    double const* __restrict__ s, double const* __restrict__ t, double const* __restrict__ phat,
+                                                    double const* __restrict__ shat, double const* __restrict__ rhat, double* __restrict__ part,
+                                                    KryScalars const* S) {
+  __shared__ double sm[TPB / 64];
+  if (S->stop) return;
+  double const alpha = S->alpha, omega = S->omega;
+  double d0 = 0., d1 = 0.;
+  for (size_t j = blockIdx.x * (size_t)TPB + threadIdx.x; j < nu + np_; j += (size_t)gridDim.x * TPB) {
+    size_t const i = j < nu ? j : n0 + (j - nu);
+    x[i] += alpha * phat[i] + omega * shat[i];
+    double const rn = s[i] - omega * t[i];
+    r[i] = rn;
+    d0 += rhat[i] * rn;
+    d1 += rn * rn;
+  }
+  double const s0 = block_sum(d0, sm);
+  double const s1 = block_sum(d1, sm);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s0;
+    part[gridDim.x + blockIdx.x] = s1;
+  }
+}
+
+// one block adds this part's partials in the fixed order of k_reduce: sums[0] (and sums[1] for KIND 1, 2), to be
+// all-reduced over the parts.  KIND as in k_reduce.
+template <int KIND>
+__global__ void __launch_bounds__(TPB) k_sums(double const* __restrict__ part, int nb, double* __restrict__ sums, KryScalars const* S) {
+  __shared__ double sm[TPB / 64];
+  if (KIND != 3 && S->stop) return;
+  double a0 = 0., a1 = 0.;
+  for (int b = threadIdx.x; b < nb; b += TPB) a0 += part[b];
+  if (KIND == 1 || KIND == 2)
+    for (int b = threadIdx.x; b < nb; b += TPB) a1 += part[nb + b];
+  double const s0 = block_sum(a0, sm);
+  double const s1 = (KIND == 1 || KIND == 2) ? block_sum(a1, sm) : 0.;
+  if (threadIdx.x != 0) return;
+  sums[0] = s0;
+  if (KIND == 1 || KIND == 2) sums[1] = s1;
+}
+
+// the scalars of the recurrence from the GLOBAL sums (the formulas of k_reduce): the same on every rank
+template <int KIND>
+__global__ void __launch_bounds__(64) k_scalars(double const* __restrict__ sums, double tol2, KryScalars* S) {
+  if (threadIdx.x != 0 || (KIND != 3 && S->stop)) return;
+  double const s0 = sums[0], s1 = (KIND == 1 || KIND == 2) ? sums[1] : 0.;
+  if (KIND == 0) {
+    double const alpha = S->rho / s0;
+    if (!finite_d(alpha) || !(fabs(s0) >= BREAKDOWN)) S->stop = 2;
+    else S->alpha = alpha;
+  } else if (KIND == 1) {
+    double const omega = s0 / s1;
+    if (!finite_d(omega) || !(fabs(omega) >= BREAKDOWN)) S->stop = 2;
+    else S->omega = omega;
+  } else if (KIND == 2) {
+    S->rr = s1;
+    S->iters += 1;
+    if (s1 <= tol2) S->stop = 1;
+    else if (!finite_d(s1) || !finite_d(s0) || !(fabs(s0) >= BREAKDOWN)) S->stop = 2;
+    else {
+      S->beta = (s0 / S->rho) * (S->alpha / S->omega);
+      S->rho = s0;
+    }
+  } else {
+    S->rr = s0;
+    S->rho = s0;
+    S->beta = 0.;
+    S->alpha = 1.;
+    S->omega = 1.;
+    S->stop = 0;
+  }
+}
+
+// ---- host side of the multi-part solve.  A rank that meets a device error goes on through the collective sequence of the
+// batch as a bystander (`failed`: no device work, the transport's degraded entries) and reports at the next host read, where
+// all ranks leave together: a rank that stopped exchanging on its own would hang the others.
+struct Parts {
+  Solve q;
+  c8_halo* h = nullptr;
+  c8_comm* cm = nullptr;
+  int rank = 0, nranks = 1;
+  int nown = 0, n_int = 0, n_bnd = 0, nb_own = 0, nb_int = 0, nb_bnd = 0, nb_upd = 0;
+  int32_t const* list = nullptr;
+  double* sums = nullptr;
+  double *x1 = nullptr, *phat1 = nullptr, *shat1 = nullptr;  // the p segments (null with one residual)
+  bool failed = false;
+  std::string err;
+  void note(int rc) {
+    if (rc != C8_OK && !failed) { failed = true; err = c8_last_error(); }
+  }
+  void hip(hipError_t e, char const* what) {
+    if (e != hipSuccess && !failed) { failed = true; err = std::string(what) + ": " + hipGetErrorString(e); }
+  }
+};
+#define C8_PARTS_LAUNCH(P, kernel, grid, block, ...)                        \
+  do {                                                                      \
+    if (!(P).failed && (grid) > 0) {                                        \
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (P).q.c->stream, __VA_ARGS__); \
+      (P).hip(hipGetLastError(), #kernel);                                  \
+    }                                                                       \
+  } while (0)
+
+// all-reduce of the n local sums and the scalars of KIND from the global ones
+template <int KIND>
+void parts_scalars(Parts& P, int nb) {
+  C8_PARTS_LAUNCH(P, (k_sums<KIND>), 1, TPB, P.q.part, nb, P.sums, P.q.S);
+  P.note(c8_comm_allreduce_device(P.cm, P.q.c->stream, P.sums, (KIND == 1 || KIND == 2) ? 2 : 1, P.failed));
+  C8_PARTS_LAUNCH(P, (k_scalars<KIND>), 1, 64, P.sums, P.q.tol2, P.q.S);
+}
+
+// y = A x over the owned rows, the import of x's copies overlapped with the interior rows
+template <int ND, int NRES, int G, int MODE>
+void parts_spmv(Parts& P, double* x, double* x1, double* y, double const* a0) {
+  Solve const& q = P.q;
+  int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
+  int const nslots = P.nb_int + P.nb_bnd;
+  P.note(c8_halo_import_start(P.h, x, x1, P.failed));
+  C8_PARTS_LAUNCH(P, (k_spmv_list<ND, NRES, G, MODE>), xcd_grid(P.nb_int), TPB, P.list, P.n_int, q.nn, P.nb_int, 0, nslots, np, na, q.A, x, y, a0,
+                  q.part, q.S);
+  P.note(c8_halo_import_finish(P.h, x, x1, P.failed));
+  C8_PARTS_LAUNCH(P, (k_spmv_list<ND, NRES, G, MODE>), xcd_grid(P.nb_bnd), TPB, P.list + P.n_int, P.n_bnd, q.nn, P.nb_bnd, P.nb_int, nslots, np, na,
+                  q.A, x, y, a0, q.part, q.S);
+}
+
+template <int ND, int NRES>
+void parts_setup(Parts& P) {
+  Solve const& q = P.q;
+  C8_PARTS_LAUNCH(P, (k_setup<ND, NRES>), xcd_grid(P.nb_own), TPB, P.nown, P.nb_own, q.c->d_nodeptr, q.c->d_nodeadj, q.A, q.minv, q.S);
+}
+
+// r = b - A x on the owned rows (x imported first), the scalars of a fresh recurrence; S->rr = |b - A x|^2 over all parts
+template <int ND, int NRES>
+void parts_residual(Parts& P) {
+  Solve const& q = P.q;
+  P.note(c8_halo_import_start(P.h, q.x, P.x1, P.failed));
+  P.note(c8_halo_import_finish(P.h, q.x, P.x1, P.failed));
+  C8_PARTS_LAUNCH(P, (k_true_residual_own<ND, NRES>), xcd_grid(P.nb_own), TPB, P.nown, q.nn, P.nb_own, q.c->d_nodeptr, q.c->d_nodeadj, q.A, q.x,
+                  q.b0, q.b1, q.r, q.rhat, q.p, q.v, q.part);
+  parts_scalars<3>(P, P.nb_own);
+}
+
+template <int ND, int NRES, int G>
+void parts_iteration(Parts& P) {
+  Solve const& q = P.q;
+  size_t const n0 = (size_t)q.nn * ND;
+  C8_PARTS_LAUNCH(P, (k_prec_own<ND, NRES, 0>), xcd_grid(P.nb_own), TPB, P.nown, q.nn, P.nb_own, q.minv, q.r, q.v, q.p, q.phat, q.S);
+  parts_spmv<ND, NRES, G, 0>(P, q.phat, P.phat1, q.v, q.rhat);
+  parts_scalars<0>(P, P.nb_int + P.nb_bnd);
+  C8_PARTS_LAUNCH(P, (k_prec_own<ND, NRES, 1>), xcd_grid(P.nb_own), TPB, P.nown, q.nn, P.nb_own, q.minv, q.r, q.v, q.s, q.shat, q.S);
+  parts_spmv<ND, NRES, G, 1>(P, q.shat, P.shat1, q.t, q.s);
+  parts_scalars<1>(P, P.nb_int + P.nb_bnd);
+  C8_PARTS_LAUNCH(P, k_update_own, P.nb_upd, TPB, (size_t)P.nown * ND, NRES == 2 ? (size_t)P.nown : (size_t)0, n0, q.x, q.r, q.s, q.t, q.phat,
+                  q.shat, q.rhat, q.part, q.S);
+  parts_scalars<2>(P, P.nb_upd);
+}
+
+struct PartsLaunchers {
+  void (*setup)(Parts&);
+  void (*residual)(Parts&);
+  void (*iteration)(Parts&);
+  int group;
+};
+template <int ND, int NRES, int G>
+PartsLaunchers parts_launchers() { return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>, parts_iteration<ND, NRES, G>, G}; }
+
+// The host read of the scalars, COLLECTIVE: the ranks all-reduce (iterations, stop flag, their squares, failure marker).
+// Every rank sees the same five sums, so all of them return the same code: C8_ERR_DEVICE when a rank failed, or when the
+// iteration counts or stop flags are not the same everywhere (n * sum of squares = square of the sum only for equal values).
+int parts_read(Parts& P, KryScalars* h) {
+  if (!P.failed) {
+    P.hip(hipMemcpyAsync(h, P.q.S, sizeof(KryScalars), hipMemcpyDeviceToHost, P.q.c->stream), "hipMemcpyAsync");
+    if (!P.failed) P.hip(hipStreamSynchronize(P.q.c->stream), "hipStreamSynchronize");
+  }
+  double const it = P.failed ? 0. : (double)h->iters, st = P.failed ? 0. : (double)h->stop;
+  double v[5] = {it, st, it * it, st * st, P.failed ? 1. : 0.};
+  if (c8_comm_allreduce_sum(P.cm, v, 5) != C8_OK) return C8_ERR_DEVICE;  // (the message is the transport's)
+  if (v[4] > 0.)
+    return fail(C8_ERR_DEVICE, P.failed ? "c8_krylov_solve_parts: rank " + std::to_string(P.rank) + ": " + P.err
+                                        : std::string("c8_krylov_solve_parts: another rank met a device error; all ranks leave the solve"));
+  if (!(P.nranks * v[2] == v[0] * v[0]) || !(P.nranks * v[3] == v[1] * v[1]))
+    return fail(C8_ERR_DEVICE, "c8_krylov_solve_parts: the ranks disagree on the iteration count or the stop flag (this rank: " +
+                               std::to_string(h->iters) + ", " + std::to_string(h->stop) + "); all ranks leave the solve");
+  return C8_OK;
+}
+
+// the two node lists of A x, from the host graph: owned nodes with owned columns only, then the others
+int build_part_lists(c8_ctx* c) {
+  int const nown = c8_halo_num_owned(c->halo);
+  if (c->kry_list_owned == nown && (nown == 0 || c->d_kry_list)) return C8_OK;
+  std::vector<int32_t> interior, boundary;
+  for (int n = 0; n < nown; ++n) {
+    bool inner = true;
+    for (int32_t k = c->graph.nodeptr[n]; k < c->graph.nodeptr[n + 1]; ++k) inner = inner && c->graph.nodeadj[k] < nown;
+    (inner ? interior : boundary).push_back(n);
+  }
+  c->kry_n_interior = (int)interior.size();
+  c->kry_list = interior;
+  c->kry_list.insert(c->kry_list.end(), boundary.begin(), boundary.end());
+  if (c->d_kry_list) C8_HIP(hipFree(c->d_kry_list));
+  c->d_kry_list = nullptr;
+  c->kry_list_owned = -1;
+  if (nown > 0) {
+    C8_HIP(hipMalloc((void**)&c->d_kry_list, (size_t)nown * sizeof(int32_t)));
+    C8_HIP(hipMemcpy(c->d_kry_list, c->kry_list.data(), (size_t)nown * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  c->kry_list_owned = nown;
+  return C8_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -454,7 +817,7 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   if (c->halo) {
     if (info) info->status = C8_ERR_UNSUPPORTED;
     return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: a halo is attached to the context; the multi-part solve (halo exchange inside A x, "
-                                    "inner products summed over the parts) is not implemented");
+                                    "inner products summed over the parts) is c8_krylov_solve_parts, a collective call");
   }
   int const max_iters = (opts && opts->max_iters > 0) ? opts->max_iters : 20000;
   int const check_every = (opts && opts->check_every > 0) ? opts->check_every : 10;
@@ -554,6 +917,151 @@ int c8_krylov_linear_solve(void* user, const c8_system* sys, double* const dx[2]
   u->total_iters += u->info.iters;
   u->solves += 1;
   return rc;
+}
+
+// ---- the solve over the parts of a multi-part mesh ---------------------------------------------------------------------
+static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info);
+int c8_krylov_solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info) {
+  if (c && !c->halo) return c8_krylov_solve(c, sys, dx, opts, info);
+  int const rc = solve_parts(c, sys, dx, opts, info);
+  if (info) info->status = rc;
+  return rc;
+}
+static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts, c8_krylov_info* info) {
+  if (info) *info = c8_krylov_info{0, 0, C8_ERR_ARG, 0., 0.};
+  // (argument errors are the caller's on every rank alike: they return before anything is exchanged)
+  if (!c || !sys || !dx) return fail(C8_ERR_ARG, "c8_krylov_solve_parts: null argument");
+  bool const two = c->nres == 2;
+  if (!sys->A[0][0] || !sys->b[0] || !dx[0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1] || !sys->b[1] || !dx[1])))
+    return fail(C8_ERR_ARG, "c8_krylov_solve_parts: null array in the system or in dx");
+  int const max_iters = (opts && opts->max_iters > 0) ? opts->max_iters : 20000;
+  int const check_every = (opts && opts->check_every > 0) ? opts->check_every : 10;
+  int const max_restarts = (opts && opts->max_restarts > 0) ? opts->max_restarts : 5;
+  double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
+  double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
+
+  PartsLaunchers L;
+  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>();
+  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>();
+  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>();
+  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve_parts: no kernels for this number of dimensions and residuals");
+  int const nb = c->ndims + (two ? 1 : 0);
+
+  Parts P;
+  Solve& q = P.q;
+  q = Solve{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve_parts: empty mesh");
+  P.h = c->halo;
+  P.cm = c8_halo_comm(c->halo);
+  P.rank = c8_halo_rank(c->halo);
+  P.nranks = c8_halo_num_ranks(c->halo);
+  P.nown = c8_halo_num_owned(c->halo);
+  size_t const n0 = (size_t)q.nn * c->ndims;
+  q.n = n0 + (two ? (size_t)q.nn : 0);
+  // from here on every rank goes through the same sequence of collectives, whatever happens to it
+  P.note(build_part_lists(c));
+  P.n_int = c->kry_n_interior;
+  P.n_bnd = P.nown - P.n_int;
+  int const npb = TPB / L.group;
+  P.nb_own = (P.nown + TPB - 1) / TPB;
+  P.nb_int = (P.n_int + npb - 1) / npb;
+  P.nb_bnd = (P.n_bnd + npb - 1) / npb;
+  P.nb_upd = (int)std::min<size_t>(std::max<size_t>(((size_t)P.nown * nb + TPB - 1) / TPB, 1), (size_t)UPDATE_MAX_BLOCKS);
+  P.note(grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * nb * nb));
+  P.note(grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n));
+  P.note(grow(&c->d_kry_part, &c->kry_part_n, 2 * (size_t)std::max(std::max(P.nb_int + P.nb_bnd, P.nb_upd), std::max(P.nb_own, 1))));
+  if (!c->d_kry_scalars) P.hip(hipMalloc(&c->d_kry_scalars, sizeof(KryScalars)), "hipMalloc");
+  if (!c->d_kry_sums) P.hip(hipMalloc((void**)&c->d_kry_sums, 64 * sizeof(double)), "hipMalloc");
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  q.b0 = sys->b[0];
+  q.b1 = sys->b[1];
+  double* vec = c->d_kry_vec;
+  q.x = vec, q.r = vec + q.n, q.rhat = vec + 2 * q.n, q.p = vec + 3 * q.n, q.v = vec + 4 * q.n, q.s = vec + 5 * q.n;
+  q.t = vec + 6 * q.n, q.phat = vec + 7 * q.n, q.shat = vec + 8 * q.n;
+  q.part = c->d_kry_part;
+  q.minv = c->d_kry_minv;
+  q.S = (KryScalars*)c->d_kry_scalars;
+  P.list = c->d_kry_list;
+  P.sums = c->d_kry_sums;
+  P.x1 = two ? q.x + n0 : nullptr;
+  P.phat1 = two ? q.phat + n0 : nullptr;
+  P.shat1 = two ? q.shat + n0 : nullptr;
+
+  // set-up: the inverses of the owned diagonal blocks (complete after the gather), x = 0, r = rhat = b
+  KryScalars h{};
+  h.bad_node = INT_MAX;
+  if (!P.failed) P.hip(hipMemcpyAsync(q.S, &h, sizeof(h), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
+  if (!P.failed) P.hip(hipMemsetAsync(vec, 0, 9 * q.n * sizeof(double), c->stream), "hipMemsetAsync");  // the copies' entries too
+  L.setup(P);
+  L.residual(P);
+  int rc;
+  if ((rc = parts_read(P, &h)) != C8_OK) return rc;
+  {  // the bad-node decision over the ranks: slot r holds rank r's smallest bad node + 1
+    std::vector<double> bad(P.nranks, 0.);
+    if (h.bad_node != INT_MAX) bad[P.rank] = (double)h.bad_node + 1.;
+    if ((rc = c8_comm_allreduce_sum(P.cm, bad.data(), P.nranks)) != C8_OK) return rc;
+    for (int r = 0; r < P.nranks; ++r)
+      if (bad[r] > 0.)
+        return fail(C8_ERR_ARG, "c8_krylov_solve_parts: the diagonal block of node " + std::to_string((long long)bad[r] - 1) + " (local id) of rank " +
+                                std::to_string(r) + " is singular or not finite (node-block Jacobi preconditioner)");
+  }
+  double const b_norm = std::sqrt(h.rr);  // of the global owned system: the same on every rank
+  if (!std::isfinite(b_norm)) return fail(C8_ERR_ARG, "c8_krylov_solve_parts: the right-hand side or the matrix is not finite");
+  auto store = [&]() -> int {
+    C8_HIP(hipMemcpyAsync(dx[0], q.x, n0 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (two) C8_HIP(hipMemcpyAsync(dx[1], q.x + n0, (size_t)q.nn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return C8_OK;
+  };
+  if (b_norm == 0.) {
+    if (info) *info = c8_krylov_info{0, 0, C8_OK, 0., 0.};
+    return store();
+  }
+  double const tol = std::max(rel_tol * b_norm, abs_tol);
+  q.tol2 = tol * tol;
+
+  int restarts = 0, status = C8_NOT_CONVERGED;
+  double true_norm = b_norm;
+  while (true) {
+    int const batch = std::min(check_every, max_iters - h.iters);
+    for (int k = 0; k < batch; ++k) L.iteration(P);
+    if ((rc = parts_read(P, &h)) != C8_OK) return rc;
+    if (h.stop == 0 && h.iters < max_iters) continue;
+    int const iters = h.iters;
+    L.residual(P);
+    if ((rc = parts_read(P, &h)) != C8_OK) return rc;
+    true_norm = std::sqrt(h.rr);
+    if (true_norm <= tol) { status = C8_OK; break; }
+    if (iters >= max_iters || restarts >= max_restarts || !std::isfinite(true_norm)) break;
+    restarts++;
+  }
+  if (info) *info = c8_krylov_info{h.iters, restarts, status, b_norm, true_norm};
+  if ((rc = store()) != C8_OK) return rc;
+  if (status != C8_OK)
+    return fail(C8_NOT_CONVERGED, "c8_krylov_solve_parts: |b - A x| / |b| = " + std::to_string(true_norm / b_norm) + " after " +
+                                  std::to_string(h.iters) + " iterations and " + std::to_string(restarts) + " restarts");
+  return C8_OK;
+}
+
+int c8_krylov_linear_solve_parts(void* user, const c8_system* sys, double* const dx[2]) {
+  c8_krylov_user* u = (c8_krylov_user*)user;
+  if (!u || !u->ctx) return fail(C8_ERR_ARG, "c8_krylov_linear_solve_parts: user must point to a c8_krylov_user with its ctx set");
+  int const rc = c8_krylov_solve_parts(u->ctx, sys, dx, &u->opts, &u->info);
+  u->total_iters += u->info.iters;
+  u->solves += 1;
+  return rc;
+}
+
+int c8_krylov_part_lists(c8_ctx* c, int32_t* num_interior, int32_t* num_boundary, const int32_t** nodes) {
+  if (!c || !num_interior || !num_boundary || !nodes) return fail(C8_ERR_ARG, "c8_krylov_part_lists: null argument");
+  if (!c->halo) return fail(C8_ERR_ARG, "c8_krylov_part_lists: no halo is attached to the context");
+  int const rc = build_part_lists(c);
+  if (rc != C8_OK) return rc;
+  *num_interior = c->kry_n_interior;
+  *num_boundary = (int32_t)c->kry_list.size() - c->kry_n_interior;
+  *nodes = c->kry_list.data();
+  return C8_OK;
 }
 
 }  // extern "C"

@@ -178,6 +178,9 @@ SYMBOLS = [
                                         C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_krylov_solve", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p), C.POINTER(KrylovOpts), C.POINTER(KrylovInfo)]),
     ("c8_krylov_linear_solve", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p)]),
+    ("c8_krylov_solve_parts", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p), C.POINTER(KrylovOpts), C.POINTER(KrylovInfo)]),
+    ("c8_krylov_linear_solve_parts", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p)]),
+    ("c8_krylov_part_lists", C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(i32p)]),
     ("c8_transform_params", C.c_int, [C.c_int, dp, i32p, dp, dp, C.c_int, dp]),
     ("c8_transform_gradient", C.c_int, [C.c_int, dp, dp, i32p, dp, dp, dp]),
     ("c8_brick_mesh", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, i32p]),

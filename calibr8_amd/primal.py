@@ -3,7 +3,8 @@
 Each load step calls `c8_primal_solve_step` (C++ Newton + line search around the HIP assembly, boundary
 conditions applied on the device).  The sparse linear solve is the caller's callback -- the reference
 uses Belos/Teko/MueLu, out of scope here; `scipy_solver` below is the direct solve on the host (the default),
-`device_solver` the library's own preconditioned BiCGStab, which keeps the system on the device.
+`device_solver` the library's own preconditioned BiCGStab, which keeps the system on the device
+(`distributed_device_solver` over the parts of a multi-part mesh, beside `distributed_scipy_solver`).
 """
 import ctypes as C
 
@@ -46,12 +47,13 @@ class DeviceSolver:
     """`c8_krylov_linear_solve` with its `c8_krylov_user` block: the step drivers call the library's BiCGStab straight
     from C++, the system never leaves the device.  `last` is the c8_krylov_info of the last solve."""
 
-    def __init__(self, asm, rel_tol=1e-10, max_iters=20000, check_every=10, max_restarts=5, abs_tol=0.0):
+    def __init__(self, asm, rel_tol=1e-10, max_iters=20000, check_every=10, max_restarts=5, abs_tol=0.0, parts=False):
         self.asm = asm  # the context must outlive the callback block
         self.user = _l.KrylovUser()
         self.user.ctx = asm.h.value
         self.user.opts = _l.KrylovOpts(int(max_iters), int(check_every), int(max_restarts), float(rel_tol), float(abs_tol))
-        self.fn = C.cast(asm.L.c8_krylov_linear_solve, C.c_void_p)
+        # parts: the collective solve over the parts of the halo attached to the context (c8_krylov_linear_solve_parts)
+        self.fn = C.cast(asm.L.c8_krylov_linear_solve_parts if parts else asm.L.c8_krylov_linear_solve, C.c_void_p)
 
     @property
     def last(self):
@@ -70,8 +72,18 @@ class DeviceSolver:
 def device_solver(asm, rel_tol=1e-10, max_iters=20000, **opts):
     """Linear solve on the device: right-preconditioned BiCGStab with node-block Jacobi (c8_krylov_solve).  Usable wherever
     `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem, FEMUProblem.
-    opts: check_every, max_restarts, abs_tol (c8_krylov_opts).  One part only: a context with a halo is refused."""
+    opts: check_every, max_restarts, abs_tol (c8_krylov_opts).  One part only: a context with a halo is refused
+    (`distributed_device_solver` is the solve over parts)."""
     return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, **opts)
+
+
+def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, **opts):
+    """Linear solve on the device over the parts of a multi-part mesh (c8_krylov_solve_parts): the BiCGStab of
+    `device_solver` with the halo import inside A x and the inner products all-reduced over the halo's communicator; every
+    rank's owned rows stay on its device.  Usable wherever `distributed_scipy_solver(asm, plan, dist)` is: PrimalDriver,
+    hence adjoint_gradient, InverseProblem and FEMUProblem over parts.  `asm` is the part's assembler, with its Halo attached
+    before the first solve; every rank must make the same calls (the solve is collective).  opts as for `device_solver`."""
+    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, **opts)
 
 
 def _callback(solver):

@@ -388,8 +388,8 @@ typedef struct {
  * may be NULL.  Returns C8_OK; C8_NOT_CONVERGED with dx holding the last iterate and info filled; C8_ERR_ARG for null
  * pointers, a right-hand side that is not finite, or a node whose diagonal block is singular or not finite (the
  * message of c8_last_error names the node; nothing is iterated); C8_ERR_UNSUPPORTED when a halo is attached to the
- * context: a multi-part solve needs the halo exchange inside A x and inner products summed over the parts, which this
- * solver does not have.  b = 0 returns dx = 0 after 0 iterations. */
+ * context: a multi-part solve needs the halo exchange inside A x and inner products summed over the parts, which is
+ * c8_krylov_solve_parts below.  b = 0 returns dx = 0 after 0 iterations. */
 int c8_krylov_solve(c8_ctx* ctx, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts,
                     c8_krylov_info* info);
 /* The same as a c8_linear_solve_fn for c8_primal_solve_step / c8_adjoint_solve_step: `user` points to a
@@ -401,6 +401,29 @@ typedef struct {
   int64_t total_iters, solves;
 } c8_krylov_user;
 int c8_krylov_linear_solve(void* user, const c8_system* sys, double* const dx[2]);
+/* The same solve over the parts of a multi-part mesh (a halo attached to the context, c8_halo_attach).  COLLECTIVE: every
+ * rank of the halo's communicator calls it with its local system as the step drivers hold it after c8_halo_gather: the
+ * first num_owned node rows are the owned system, columns address owned, ghost and phantom local ids, ghost rows are
+ * scratch.  A x runs over the owned rows with the import (C3) of the multiplied vector inside it: the rows without a ghost
+ * or phantom column are multiplied while the messages travel, the others afterwards.  Inner products are local partials in
+ * a fixed order, then one all-reduce of the 1-2 sums through the communicator (device buffers under RCCL: ncclAllReduce on
+ * the communicator's stream, ordered by events, no host wait; copy down / callback / copy up under the host transport): three
+ * all-reduces and two imports per iteration.  Every scalar and the stop flag derive from all-reduced values only, and at
+ * every host read the ranks all-reduce (iterations, stop flag, failure marker): ranks that disagree, or a rank with a
+ * device error, make EVERY rank return C8_ERR_DEVICE instead of entering another batch.  dx is written on the owned nodes
+ * (ghost and phantom entries unspecified: the drivers import them afterwards); info->b_norm and info->residual_norm are
+ * norms of the global owned system; iters, restarts and status are the same on all ranks, and so is the return value of
+ * the refusals of a non-finite right-hand side and of a singular diagonal block (the message names the node by local id
+ * and rank).  For one partition the result is a pure function of the inputs and of the transport's all-reduce (no
+ * floating-point atomics).  Without a halo the call is c8_krylov_solve. */
+int c8_krylov_solve_parts(c8_ctx* ctx, const c8_system* sys, double* const dx[2], const c8_krylov_opts* opts,
+                          c8_krylov_info* info);
+/* ... as a c8_linear_solve_fn (`user` points to a c8_krylov_user), for the step drivers over parts. */
+int c8_krylov_linear_solve_parts(void* user, const c8_system* sys, double* const dx[2]);
+/* Diagnostic / test access: the two node lists of the multi-part A x (HOST array owned by the context, built from the
+ * graph at the first use; needs a halo): nodes[0 .. num_interior) are the owned nodes whose graph row has only owned
+ * columns, nodes[num_interior .. num_interior + num_boundary) the other owned nodes. */
+int c8_krylov_part_lists(c8_ctx* ctx, int32_t* num_interior, int32_t* num_boundary, const int32_t** nodes);
 
 /* ---- multi-part meshes: owned/ghost halo and reductions ---------------------------------
  * One process per GPU, one mesh part per process, elements not ghosted, nodes on part boundaries shared -- the
