@@ -197,6 +197,18 @@ class Assembler:
     def scatter(self):
         return {_l.C8_SCATTER_COLORED: "colored", _l.C8_SCATTER_ATOMIC: "atomic", _l.C8_SCATTER_GATHER: "gather"}[self.L.c8_get_scatter_mode(self.h)]
 
+    def set_krylov_preconditioner(self, kind, sweeps=1):
+        """Preconditioner of the device solves on this assembler: "jacobi" (node-block Jacobi, the default) or "sgs"
+        (`sweeps` symmetric multicolour node-block Gauss-Seidel sweeps; c8_krylov_set_preconditioner)."""
+        kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS}
+        if kind not in kinds:
+            raise ValueError("preconditioner must be 'jacobi' or 'sgs', not %r" % (kind,))
+        _l.check(self.L.c8_krylov_set_preconditioner(self.h, kinds[kind], int(sweeps)))
+
+    @property
+    def krylov_preconditioner(self):
+        return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
+
     def set_assign_mode(self, on):
         """scatter='gather': Jacobian assemblies assign A and b (zero_all + assembly in one call) instead of adding"""
         _l.check(self.L.c8_set_assign_mode(self.h, int(bool(on))))

@@ -106,6 +106,13 @@ struct c8_ctx {
   int kry_n_interior = 0;
   int32_t* d_kry_list = nullptr;
   double* d_kry_sums = nullptr;      // the local sums of an inner product, all-reduced in place
+  // ... preconditioner of both solves (c8_krylov_set_preconditioner) and the colour lists of the Gauss-Seidel sweeps:
+  // nodes kry_color_nodes[kry_color_ptr[c] .. kry_color_ptr[c + 1]) have colour c (ascending); all nodes, or the owned
+  // nodes coloured over the owned sub-graph when a halo is attached
+  int kry_precond = C8_PRECOND_BLOCK_JACOBI, kry_sweeps = 1;
+  std::vector<int32_t> kry_color_ptr, kry_color_nodes;
+  int kry_colors_for = -2;           // what the colour lists were built for: -1 no halo, else num_owned (-2: not built)
+  int32_t* d_kry_colors = nullptr;   // device mirror of kry_color_nodes
 };
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
 int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);

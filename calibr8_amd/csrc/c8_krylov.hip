@@ -15,6 +15,10 @@
 //   stop      once the recursive residual meets the tolerance (stop = 1) or a breakdown is seen (stop = 2) every later
 //             kernel of the batch returns at once: x and the iteration count stay those of that iteration
 //
+// With c8_krylov_set_preconditioner(C8_PRECOND_BLOCK_SGS) the two k_prec launches become k_vec (the vector update alone,
+// out = 0) followed by the multicolour Gauss-Seidel sweeps of k_sgs_color, one launch per colour;
+// every other launch of the iteration is the same.
+//
 // Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
 // the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
 // entries are addressable and the halo's import tables apply to {v, v + nnodes * ND}; every kernel runs over the OWNED
@@ -365,6 +369,83 @@ __global__ void __launch_bounds__(TPB) k_reduce(double const* __restrict__ part,
   }
 }
 
+// ---- multicolour node-block Gauss-Seidel (c8_krylov_set_preconditioner).  One launch per colour:
+//   x_i <- x_i + D_i^-1 (rhs_i - sum_j A_ij x_j)   for the nodes i of list[0 .. nlist), j over the columns < colbound
+// of the node's graph row.  Lane mapping of k_spmv_list (G lanes per node over the neighbours, all NB rows at once, a
+// butterfly over the G lanes); lane ri < NB of the node then forms row ri of D_i^-1 (rhs_i - sum) and adds it to x in place.
+// No two nodes of a list are neighbours, so every x entry a launch reads from another node is one it does not write: x is
+// read and written through the same plain pointer (no __restrict__, no read-only path).  A node's own entry is read by its
+// own lanes only, before the butterfly that its store depends on.  colbound = the number of local nodes, or num_owned
+// for the part-local operator (ghost and phantom columns dropped).
+template <int ND, int NRES, int G>
+__global__ void __launch_bounds__(TPB) k_sgs_color(int32_t const* __restrict__ list, int nlist, int nn, int nblocks, int colbound,
+                                                   int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj, Blocks A,
+                                                   double const* __restrict__ minv, double const* __restrict__ rhs, double* x,
+                                                   KryScalars const* S) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  constexpr int NPB = TPB / G;
+  if (S->stop) return;
+  int const lb = xcd_block(blockIdx.x, nblocks);
+  if (lb >= nblocks) return;
+  int const li = lb * NPB + threadIdx.x / G, lane = threadIdx.x % G;
+  bool const live = li < nlist;
+  int const node = live ? list[li] : 0;
+  size_t const n0 = (size_t)nn * ND;
+  double acc[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) acc[k] = 0.;
+  if (live) {
+    int64_t const np = nodeptr[node];
+    int const deg = (int)(nodeptr[node + 1] - np);
+    for (int k = lane; k < deg; k += G) {
+      int const cn = nodeadj[np + k];
+      if (cn >= colbound) continue;
+      double xv[NB];
+#pragma unroll
+      for (int e = 0; e < NB; ++e) xv[e] = x[e < ND ? (size_t)cn * ND + e : n0 + cn];
+#pragma unroll
+      for (int ri = 0; ri < ND; ++ri) {
+        double const* row = A.A00 + np * ND * ND + (int64_t)ri * deg * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[ri] += row[e] * xv[e];
+        if (NRES == 2) acc[ri] += A.A01[np * ND + (int64_t)ri * deg + k] * xv[NB - 1];
+      }
+      if (NRES == 2) {
+        double const* row = A.A10 + np * ND + (int64_t)k * ND;
+#pragma unroll
+        for (int e = 0; e < ND; ++e) acc[NB - 1] += row[e] * xv[e];
+        acc[NB - 1] += A.A11[np + k] * xv[NB - 1];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k)
+    for (int o = G / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, G);
+  if (live && lane < NB) {
+    double const* m = minv + (size_t)node * NB * NB + lane * NB;
+    double d = 0.;
+#pragma unroll
+    for (int cj = 0; cj < NB; ++cj) d += m[cj] * (rhs[cj < ND ? (size_t)node * ND + cj : n0 + node] - acc[cj]);
+    size_t const idx = lane < ND ? (size_t)node * ND + lane : n0 + node;
+    x[idx] += d;
+  }
+}
+
+// ---- the vector update of k_prec without its preconditioner apply, over the two owned ranges of k_update_own; out = 0
+// is the start of the Gauss-Seidel sweeps that follow
+//   SECOND = 0:  p = r + beta (p - omega v)  (in place, w = p)        SECOND = 1:  s = r - alpha v  (w = s)
+template <int SECOND>
+__global__ void __launch_bounds__(TPB) k_vec(size_t nu, size_t np_, size_t n0, double const* __restrict__ r, double const* __restrict__ v,
+                                             double* __restrict__ w, double* __restrict__ out, KryScalars const* S) {
+  if (S->stop) return;
+  double const alpha = S->alpha, omega = S->omega, beta = S->beta;
+  for (size_t j = blockIdx.x * (size_t)TPB + threadIdx.x; j < nu + np_; j += (size_t)gridDim.x * TPB) {
+    size_t const i = j < nu ? j : n0 + (j - nu);
+    w[i] = SECOND ? r[i] - alpha * v[i] : r[i] + beta * (w[i] - omega * v[i]);
+    out[i] = 0.;
+  }
+}
+
 template <class T>
 int grow(T** buf, size_t* have, size_t need) {
   if (need <= *have) return C8_OK;
@@ -431,6 +512,59 @@ int launch_iteration(Solve const& q) {
   return C8_OK;
 }
 
+// x = M^-1 rhs by the context's number of symmetric sweeps, x = 0 on entry (k_vec): colours 0 .. nc - 1, then nc - 2 .. 0,
+// one launch each.  Every launch is the general form -- the first forward sweep reads the zeros of the colours it has not
+// reached yet -- except colour 0 of the first sweep, which reads no column at all (colbound 0: x_i = D_i^-1 rhs_i).
+template <int ND, int NRES, int G>
+hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x) {
+  c8_ctx const* c = q.c;
+  int const nc = (int)c->kry_color_ptr.size() - 1;
+  auto color = [&](int k, int bound) {
+    int const lo = c->kry_color_ptr[k], n = c->kry_color_ptr[k + 1] - lo, nblocks = (n + TPB / G - 1) / (TPB / G);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((k_sgs_color<ND, NRES, G>), dim3(xcd_grid(nblocks)), dim3(TPB), 0, c->stream, c->d_kry_colors + lo, n, q.nn, nblocks, bound,
+                       c->d_nodeptr, c->d_nodeadj, q.A, q.minv, rhs, x, q.S);
+    return hipGetLastError();
+  };
+  hipError_t e;
+  for (int s = 0; s < c->kry_sweeps; ++s) {
+    for (int k = 0; k < nc; ++k)
+      if ((e = color(k, s == 0 && k == 0 ? 0 : colbound)) != hipSuccess) return e;
+    for (int k = nc - 2; k >= 0; --k)
+      if ((e = color(k, colbound)) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// launch_iteration with the Gauss-Seidel sweeps in the place of the D^-1 multiplication
+template <int ND, int NRES, int G>
+int launch_iteration_sgs(Solve const& q) {
+  hipStream_t const st = q.c->stream;
+  int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
+  size_t const n0 = (size_t)q.nn * ND;
+  hipLaunchKernelGGL((k_vec<0>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.p, q.phat, q.S);
+  C8_HIP(hipGetLastError());
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat)));
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<0>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.s, q.shat, q.S);
+  C8_HIP(hipGetLastError());
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat)));
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<1>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_update, dim3(q.nb_upd), dim3(TPB), 0, st, q.n, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<2>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_upd, q.tol2, q.S);
+  C8_HIP(hipGetLastError());
+  return C8_OK;
+}
+
 struct Launchers {
   int (*setup)(Solve const&);
   int (*residual)(Solve const&);
@@ -438,7 +572,9 @@ struct Launchers {
   int group;
 };
 template <int ND, int NRES, int G>
-Launchers launchers() { return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>, launch_iteration<ND, NRES, G>, G}; }
+Launchers launchers(bool sgs) {
+  return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>, sgs ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>, G};
+}
 
 int read_scalars(Solve const& q, KryScalars* h) {
   C8_HIP(hipMemcpyAsync(h, q.S, sizeof(KryScalars), hipMemcpyDeviceToHost, q.c->stream));
@@ -745,6 +881,23 @@ void parts_iteration(Parts& P) {
   parts_scalars<2>(P, P.nb_upd);
 }
 
+// parts_iteration with the part-local Gauss-Seidel sweeps (columns < num_owned) in the place of the D^-1 multiplication
+template <int ND, int NRES, int G>
+void parts_iteration_sgs(Parts& P) {
+  Solve const& q = P.q;
+  size_t const n0 = (size_t)q.nn * ND, nu = (size_t)P.nown * ND, np_ = NRES == 2 ? (size_t)P.nown : (size_t)0;
+  C8_PARTS_LAUNCH(P, (k_vec<0>), P.nb_upd, TPB, nu, np_, n0, q.r, q.v, q.p, q.phat, q.S);
+  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.p, q.phat), "k_sgs_color");
+  parts_spmv<ND, NRES, G, 0>(P, q.phat, P.phat1, q.v, q.rhat);
+  parts_scalars<0>(P, P.nb_int + P.nb_bnd);
+  C8_PARTS_LAUNCH(P, (k_vec<1>), P.nb_upd, TPB, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
+  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.s, q.shat), "k_sgs_color");
+  parts_spmv<ND, NRES, G, 1>(P, q.shat, P.shat1, q.t, q.s);
+  parts_scalars<1>(P, P.nb_int + P.nb_bnd);
+  C8_PARTS_LAUNCH(P, k_update_own, P.nb_upd, TPB, nu, np_, n0, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
+  parts_scalars<2>(P, P.nb_upd);
+}
+
 struct PartsLaunchers {
   void (*setup)(Parts&);
   void (*residual)(Parts&);
@@ -752,7 +905,9 @@ struct PartsLaunchers {
   int group;
 };
 template <int ND, int NRES, int G>
-PartsLaunchers parts_launchers() { return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>, parts_iteration<ND, NRES, G>, G}; }
+PartsLaunchers parts_launchers(bool sgs) {
+  return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>, sgs ? parts_iteration_sgs<ND, NRES, G> : parts_iteration<ND, NRES, G>, G};
+}
 
 // The host read of the scalars, COLLECTIVE: the ranks all-reduce (iterations, stop flag, their squares, failure marker).
 // Every rank sees the same five sums, so all of them return the same code: C8_ERR_DEVICE when a rank failed, or when the
@@ -798,6 +953,103 @@ int build_part_lists(c8_ctx* c) {
   return C8_OK;
 }
 
+// the colour lists of the Gauss-Seidel sweeps from the host graph (greedy, ascending node id, smallest free colour) and
+// their device mirror: all nodes, or the owned nodes over the owned sub-graph when a halo is attached
+int build_colors(c8_ctx* c) {
+  int const want = c->halo ? c8_halo_num_owned(c->halo) : -1;
+  if (c->kry_colors_for == want) return C8_OK;
+  int const n = c->halo ? want : c->mesh.nnodes;
+  std::vector<int32_t> color(std::max(n, 0), -1), used;
+  int nc = 0;
+  for (int i = 0; i < n; ++i) {
+    used.assign(nc + 1, 0);
+    for (int32_t k = c->graph.nodeptr[i]; k < c->graph.nodeptr[i + 1]; ++k) {
+      int32_t const j = c->graph.nodeadj[k];
+      if (j < i && color[j] >= 0) used[color[j]] = 1;  // (j < i < n: already coloured, and owned)
+    }
+    int col = 0;
+    while (used[col]) ++col;
+    color[i] = col;
+    nc = std::max(nc, col + 1);
+  }
+  c->kry_colors_for = -2;
+  c->kry_color_ptr.assign(nc + 1, 0);
+  for (int i = 0; i < n; ++i) c->kry_color_ptr[color[i] + 1]++;
+  for (int k = 0; k < nc; ++k) c->kry_color_ptr[k + 1] += c->kry_color_ptr[k];
+  c->kry_color_nodes.assign(std::max(n, 0), 0);
+  std::vector<int32_t> at(c->kry_color_ptr.begin(), c->kry_color_ptr.end() - 1);
+  for (int i = 0; i < n; ++i) c->kry_color_nodes[at[color[i]]++] = i;
+  if (c->d_kry_colors) C8_HIP(hipFree(c->d_kry_colors));
+  c->d_kry_colors = nullptr;
+  if (n > 0) {
+    C8_HIP(hipMalloc((void**)&c->d_kry_colors, (size_t)n * sizeof(int32_t)));
+    C8_HIP(hipMemcpy(c->d_kry_colors, c->kry_color_nodes.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  c->kry_colors_for = want;
+  return C8_OK;
+}
+
+// c8_krylov_precondition: the set-up and the true-residual kernel at x = 0 give the block inverses, r = v, its norm (the
+// refusal of non-finite input) and the scalars of a fresh recurrence (alpha = 1, the work vector v = 0), with which the
+// second preconditioner step of an iteration, s = r - alpha v = v, shat = M^-1 s, is the apply asked for.  Nothing is
+// exchanged: with a halo the owned rows, and x = 0 in place of an import.
+template <int ND, int NRES, int G>
+int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
+  constexpr int NB = ND + (NRES == 2 ? 1 : 0);
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
+  Solve q{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  int const nown = c->halo ? c8_halo_num_owned(c->halo) : q.nn;
+  if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_precondition: empty mesh");
+  if (nown <= 0) return C8_OK;
+  size_t const n0 = (size_t)q.nn * ND, nu = (size_t)nown * ND, np_ = NRES == 2 ? (size_t)nown : (size_t)0;
+  q.n = n0 + (NRES == 2 ? (size_t)q.nn : 0);
+  q.nb_node = (nown + TPB - 1) / TPB;
+  q.nb_upd = (int)std::min<size_t>((nu + np_ + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
+  int rc;
+  if (sgs && (rc = build_colors(c)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * NB * NB)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_part, &c->kry_part_n, 2 * (size_t)std::max(q.nb_node, q.nb_upd))) != C8_OK) return rc;
+  if (!c->d_kry_scalars) C8_HIP(hipMalloc(&c->d_kry_scalars, sizeof(KryScalars)));
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  double* vec = c->d_kry_vec;
+  q.x = vec, q.r = vec + q.n, q.rhat = vec + 2 * q.n, q.p = vec + 3 * q.n, q.v = vec + 4 * q.n, q.s = vec + 5 * q.n;
+  q.t = vec + 6 * q.n, q.phat = vec + 7 * q.n, q.shat = vec + 8 * q.n;
+  q.part = c->d_kry_part;
+  q.minv = c->d_kry_minv;
+  q.S = (KryScalars*)c->d_kry_scalars;
+  hipStream_t const st = c->stream;
+  KryScalars h{};
+  h.bad_node = INT_MAX;
+  C8_HIP(hipMemcpyAsync(q.S, &h, sizeof(h), hipMemcpyHostToDevice, st));
+  C8_HIP(hipMemsetAsync(vec, 0, 9 * q.n * sizeof(double), st));
+  hipLaunchKernelGGL((k_setup<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nb_node, c->d_nodeptr, c->d_nodeadj, q.A, q.minv, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_true_residual_own<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nn, q.nb_node, c->d_nodeptr, c->d_nodeadj,
+                     q.A, q.x, v[0], v[1], q.r, q.rhat, q.p, q.v, q.part);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<3>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_node, 0., q.S);
+  C8_HIP(hipGetLastError());
+  if ((rc = read_scalars(q, &h)) != C8_OK) return rc;
+  if (h.bad_node != INT_MAX)
+    return fail(C8_ERR_ARG, "c8_krylov_precondition: the diagonal block of node " + std::to_string(h.bad_node) +
+                            " is singular or not finite (node-block Jacobi preconditioner)");
+  if (!std::isfinite(h.rr)) return fail(C8_ERR_ARG, "c8_krylov_precondition: the vector or the matrix is not finite");
+  if (sgs) {
+    hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
+    C8_HIP(hipGetLastError());
+    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat)));
+  } else {
+    hipLaunchKernelGGL((k_prec_own<ND, NRES, 1>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nn, q.nb_node, q.minv, q.r, q.v, q.s, q.shat, q.S);
+    C8_HIP(hipGetLastError());
+  }
+  C8_HIP(hipMemcpyAsync(y[0], q.shat, nu * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (NRES == 2) C8_HIP(hipMemcpyAsync(y[1], q.shat + n0, np_ * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return C8_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -825,10 +1077,11 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
   Launchers L;
-  if (c->ndims == 3 && two) L = launchers<3, 2, 16>();
-  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>();
-  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>();
+  if (c->ndims == 3 && two) L = launchers<3, 2, 16>(sgs);
+  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>(sgs);
+  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>(sgs);
   else {
     if (info) info->status = C8_ERR_UNSUPPORTED;
     return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: no kernels for this number of dimensions and residuals");
@@ -845,6 +1098,7 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   q.nb_upd = (int)std::min<size_t>((q.n + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve: empty mesh");
   int rc;
+  if (sgs && (rc = build_colors(c)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * nb * nb)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_part, &c->kry_part_n, 2 * (size_t)std::max(q.nb_spmv, q.nb_upd))) != C8_OK) return rc;
@@ -940,10 +1194,11 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
   PartsLaunchers L;
-  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>();
-  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>();
-  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>();
+  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(sgs);
+  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>(sgs);
+  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>(sgs);
   else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve_parts: no kernels for this number of dimensions and residuals");
   int const nb = c->ndims + (two ? 1 : 0);
 
@@ -962,6 +1217,7 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   q.n = n0 + (two ? (size_t)q.nn : 0);
   // from here on every rank goes through the same sequence of collectives, whatever happens to it
   P.note(build_part_lists(c));
+  if (sgs) P.note(build_colors(c));
   P.n_int = c->kry_n_interior;
   P.n_bnd = P.nown - P.n_int;
   int const npb = TPB / L.group;
@@ -1062,6 +1318,42 @@ int c8_krylov_part_lists(c8_ctx* c, int32_t* num_interior, int32_t* num_boundary
   *num_boundary = (int32_t)c->kry_list.size() - c->kry_n_interior;
   *nodes = c->kry_list.data();
   return C8_OK;
+}
+
+int c8_krylov_set_preconditioner(c8_ctx* c, int kind, int sweeps) {
+  if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: null context");
+  if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: a staged assembly is waiting for c8_gather_finish");
+  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS)
+    return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: unknown preconditioner " + std::to_string(kind));
+  c->kry_precond = kind;
+  c->kry_sweeps = sweeps > 0 ? sweeps : 1;
+  return C8_OK;
+}
+
+int c8_krylov_get_preconditioner(const c8_ctx* c) {
+  if (!c) return fail(C8_ERR_ARG, "c8_krylov_get_preconditioner: null context");
+  return c->kry_precond;
+}
+
+int c8_krylov_colors(c8_ctx* c, int32_t* num_colors, const int32_t** color_ptr, const int32_t** nodes) {
+  if (!c || !num_colors || !color_ptr || !nodes) return fail(C8_ERR_ARG, "c8_krylov_colors: null argument");
+  int const rc = build_colors(c);
+  if (rc != C8_OK) return rc;
+  *num_colors = (int32_t)c->kry_color_ptr.size() - 1;
+  *color_ptr = c->kry_color_ptr.data();
+  *nodes = c->kry_color_nodes.data();
+  return C8_OK;
+}
+
+int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
+  if (!c || !sys || !v || !y) return fail(C8_ERR_ARG, "c8_krylov_precondition: null argument");
+  bool const two = c->nres == 2;
+  if (!sys->A[0][0] || !v[0] || !y[0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1] || !v[1] || !y[1])))
+    return fail(C8_ERR_ARG, "c8_krylov_precondition: null array in the system, in v or in y");
+  if (c->ndims == 3 && two) return precondition<3, 2, 16>(c, sys, v, y);
+  if (c->ndims == 2 && two) return precondition<2, 2, 8>(c, sys, v, y);
+  if (c->ndims == 2 && !two) return precondition<2, 1, 8>(c, sys, v, y);
+  return fail(C8_ERR_UNSUPPORTED, "c8_krylov_precondition: no kernels for this number of dimensions and residuals");
 }
 
 }  // extern "C"

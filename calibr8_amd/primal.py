@@ -47,8 +47,11 @@ class DeviceSolver:
     """`c8_krylov_linear_solve` with its `c8_krylov_user` block: the step drivers call the library's BiCGStab straight
     from C++, the system never leaves the device.  `last` is the c8_krylov_info of the last solve."""
 
-    def __init__(self, asm, rel_tol=1e-10, max_iters=20000, check_every=10, max_restarts=5, abs_tol=0.0, parts=False):
+    def __init__(self, asm, rel_tol=1e-10, max_iters=20000, check_every=10, max_restarts=5, abs_tol=0.0, parts=False,
+                 preconditioner=None, sweeps=1):
         self.asm = asm  # the context must outlive the callback block
+        if preconditioner is not None:  # context state: it holds for every solve on this assembler (None: left as it is)
+            asm.set_krylov_preconditioner(preconditioner, sweeps)
         self.user = _l.KrylovUser()
         self.user.ctx = asm.h.value
         self.user.opts = _l.KrylovOpts(int(max_iters), int(check_every), int(max_restarts), float(rel_tol), float(abs_tol))
@@ -69,21 +72,25 @@ class DeviceSolver:
         return int(self.user.solves)
 
 
-def device_solver(asm, rel_tol=1e-10, max_iters=20000, **opts):
-    """Linear solve on the device: right-preconditioned BiCGStab with node-block Jacobi (c8_krylov_solve).  Usable wherever
-    `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem, FEMUProblem.
-    opts: check_every, max_restarts, abs_tol (c8_krylov_opts).  One part only: a context with a halo is refused
+def device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditioner="jacobi", sweeps=1, **opts):
+    """Linear solve on the device: right-preconditioned BiCGStab (c8_krylov_solve) with node-block Jacobi, or with
+    preconditioner="sgs" `sweeps` symmetric multicolour node-block Gauss-Seidel sweeps.  The preconditioner is state of the
+    assembler's context: this call SETS it (Assembler.set_krylov_preconditioner, refused while a staged assembly waits for
+    gather_finish), the default "jacobi" included, so it overrides an earlier choice and holds for every solver on `asm`.
+    Usable wherever `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem,
+    FEMUProblem.  opts: check_every, max_restarts, abs_tol (c8_krylov_opts).  One part only: a context with a halo is refused
     (`distributed_device_solver` is the solve over parts)."""
-    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, **opts)
+    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, preconditioner=preconditioner, sweeps=sweeps, **opts)
 
 
-def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, **opts):
+def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditioner="jacobi", sweeps=1, **opts):
     """Linear solve on the device over the parts of a multi-part mesh (c8_krylov_solve_parts): the BiCGStab of
     `device_solver` with the halo import inside A x and the inner products all-reduced over the halo's communicator; every
     rank's owned rows stay on its device.  Usable wherever `distributed_scipy_solver(asm, plan, dist)` is: PrimalDriver,
     hence adjoint_gradient, InverseProblem and FEMUProblem over parts.  `asm` is the part's assembler, with its Halo attached
-    before the first solve; every rank must make the same calls (the solve is collective).  opts as for `device_solver`."""
-    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, **opts)
+    before the first solve; every rank must make the same calls (the solve is collective).  preconditioner, sweeps and opts as
+    for `device_solver`; "sgs" is part-local here (columns owned by other parts are dropped inside the sweeps)."""
+    return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, preconditioner=preconditioner, sweeps=sweeps, **opts)
 
 
 def _callback(solver):
