@@ -198,16 +198,17 @@ class Assembler:
         return {_l.C8_SCATTER_COLORED: "colored", _l.C8_SCATTER_ATOMIC: "atomic", _l.C8_SCATTER_GATHER: "gather"}[self.L.c8_get_scatter_mode(self.h)]
 
     def set_krylov_preconditioner(self, kind, sweeps=1):
-        """Preconditioner of the device solves on this assembler: "jacobi" (node-block Jacobi, the default) or "sgs"
-        (`sweeps` symmetric multicolour node-block Gauss-Seidel sweeps; c8_krylov_set_preconditioner)."""
-        kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS}
+        """Preconditioner of the device solves on this assembler: "jacobi" (node-block Jacobi, the default), "sgs"
+        (`sweeps` symmetric multicolour node-block Gauss-Seidel sweeps) or "two_level" (a coarse correction with the
+        rigid-body modes of node aggregates, then `sweeps` of those sweeps; one part only); c8_krylov_set_preconditioner."""
+        kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS, "two_level": _l.C8_PRECOND_TWO_LEVEL}
         if kind not in kinds:
-            raise ValueError("preconditioner must be 'jacobi' or 'sgs', not %r" % (kind,))
+            raise ValueError("preconditioner must be 'jacobi', 'sgs' or 'two_level', not %r" % (kind,))
         _l.check(self.L.c8_krylov_set_preconditioner(self.h, kinds[kind], int(sweeps)))
 
     @property
     def krylov_preconditioner(self):
-        return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
+        return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs", _l.C8_PRECOND_TWO_LEVEL: "two_level"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
 
     def set_assign_mode(self, on):
         """scatter='gather': Jacobian assemblies assign A and b (zero_all + assembly in one call) instead of adding"""

@@ -92,7 +92,9 @@ def build(force=False, verbose=False):
         workers = max(1, min(len(jobs), int(os.environ.get("C8_BUILD_JOBS", "0")) or (os.cpu_count() or 4)))
         with ThreadPoolExecutor(workers) as pool:
             list(pool.map(run, jobs))
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
+    # rocSOLVER / rocBLAS: the dense inverse of the two-level preconditioner's coarse matrix (c8_krylov_coarse.hpp)
+    rocm_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib")
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl", "-L" + rocm_lib, "-lrocsolver", "-lrocblas"]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

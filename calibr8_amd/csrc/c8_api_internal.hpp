@@ -113,7 +113,21 @@ struct c8_ctx {
   std::vector<int32_t> kry_color_ptr, kry_color_nodes;
   int kry_colors_for = -2;           // what the colour lists were built for: -1 no halo, else num_owned (-2: not built)
   int32_t* d_kry_colors = nullptr;   // device mirror of kry_color_nodes
+  // ... the coarse level of C8_PRECOND_TWO_LEVEL (c8_krylov_coarse.hpp): aggregates of the node graph, built at first use
+  int kry_nagg = -1;                 // number of aggregates (-1: not built)
+  int kry_agg_max_nbr = 0;           // most neighbouring aggregates of one aggregate (itself included)
+  std::vector<int32_t> kry_agg_of;   // [nnodes] aggregate of a node (c8_krylov_aggregates)
+  int32_t* d_kry_agg = nullptr;      // one buffer: aggregate of a node, node lists, neighbour lists, slot of every graph entry
+  size_t kry_agg_at[6] = {0, 0, 0, 0, 0, 0};  // ... where each of them starts
+  double* d_kry_agg_off = nullptr;   // [nnodes][ndims] node - centroid of its aggregate
+  int32_t* d_kry_cflags = nullptr;   // [nnodes] constrained-row flags of the current matrix
+  double* d_kry_Ac = nullptr;        // A_c, then its inverse: dense, row-major, even leading dimension
+  double* d_kry_cvec = nullptr;      // r_c and e
+  int32_t* d_kry_ipiv = nullptr;     // pivots of the LU factorisation, then the three status words of the set-up
+  size_t kry_Ac_n = 0, kry_cvec_n = 0, kry_ipiv_n = 0;
+  void* kry_rocblas = nullptr;       // rocblas_handle of the dense inverse (workspace inside), made at first use
 };
+void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
 int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);
 

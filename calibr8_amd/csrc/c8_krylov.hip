@@ -17,7 +17,9 @@
 //
 // With c8_krylov_set_preconditioner(C8_PRECOND_BLOCK_SGS) the two k_prec launches become k_vec (the vector update alone,
 // out = 0) followed by the multicolour Gauss-Seidel sweeps of k_sgs_color, one launch per colour;
-// every other launch of the iteration is the same.
+// every other launch of the iteration is the same.  With C8_PRECOND_TWO_LEVEL the sweeps start from the coarse correction
+// x = P A_c^-1 P^T rhs instead of 0 (k_restrict, k_coarse_apply, k_prolong after k_vec; c8_krylov_coarse.hpp, DESIGN.md
+// section 13d), and the set-up of a solve forms A_c and its dense inverse.
 //
 // Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
 // the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
@@ -29,6 +31,8 @@
 // memory).  THREE ALL-REDUCES AND TWO IMPORTS PER ITERATION.  Every scalar and the stop flag derive from all-reduced
 // values only; at every host read the ranks all-reduce (iterations, stop flag, failure marker) and leave together.
 #include <hip/hip_runtime.h>
+#include <rocblas/rocblas.h>
+#include <rocsolver/rocsolver.h>
 
 #include <algorithm>
 #include <climits>
@@ -468,6 +472,8 @@ struct Solve {
   double tol2 = 0.;
 };
 
+#include "c8_krylov_coarse.hpp"
+
 template <int ND, int NRES>
 int launch_setup(Solve const& q) {
   hipLaunchKernelGGL((k_setup<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, q.c->stream, q.nn, q.nb_node, q.c->d_nodeptr,
@@ -515,8 +521,9 @@ int launch_iteration(Solve const& q) {
 // x = M^-1 rhs by the context's number of symmetric sweeps, x = 0 on entry (k_vec): colours 0 .. nc - 1, then nc - 2 .. 0,
 // one launch each.  Every launch is the general form -- the first forward sweep reads the zeros of the colours it has not
 // reached yet -- except colour 0 of the first sweep, which reads no column at all (colbound 0: x_i = D_i^-1 rhs_i).
+// from_zero = false (the two-level kind: x holds the coarse correction on entry) gives that launch the full bound too.
 template <int ND, int NRES, int G>
-hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x) {
+hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x, bool from_zero = true) {
   c8_ctx const* c = q.c;
   int const nc = (int)c->kry_color_ptr.size() - 1;
   auto color = [&](int k, int bound) {
@@ -529,7 +536,7 @@ hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x
   hipError_t e;
   for (int s = 0; s < c->kry_sweeps; ++s) {
     for (int k = 0; k < nc; ++k)
-      if ((e = color(k, s == 0 && k == 0 ? 0 : colbound)) != hipSuccess) return e;
+      if ((e = color(k, from_zero && s == 0 && k == 0 ? 0 : colbound)) != hipSuccess) return e;
     for (int k = nc - 2; k >= 0; --k)
       if ((e = color(k, colbound)) != hipSuccess) return e;
   }
@@ -565,15 +572,50 @@ int launch_iteration_sgs(Solve const& q) {
   return C8_OK;
 }
 
+// launch_iteration_sgs with the sweeps started from the coarse correction of their right-hand side
+template <int ND, int NRES, int G>
+int launch_iteration_two_level(Solve const& q) {
+  hipStream_t const st = q.c->stream;
+  int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
+  size_t const n0 = (size_t)q.nn * ND;
+  hipLaunchKernelGGL((k_vec<0>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.p, q.phat, q.S);
+  C8_HIP(hipGetLastError());
+  C8_HIP((launch_coarse<ND, NRES>(q, q.p, q.phat)));
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat, false)));
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<0>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.s, q.shat, q.S);
+  C8_HIP(hipGetLastError());
+  C8_HIP((launch_coarse<ND, NRES>(q, q.s, q.shat)));
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat, false)));
+  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
+                     q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<1>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_update, dim3(q.nb_upd), dim3(TPB), 0, st, q.n, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
+  C8_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_reduce<2>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_upd, q.tol2, q.S);
+  C8_HIP(hipGetLastError());
+  return C8_OK;
+}
+
 struct Launchers {
   int (*setup)(Solve const&);
   int (*residual)(Solve const&);
   int (*iteration)(Solve const&);
+  int (*coarse)(Solve const&, bool);  // the coarse level of the two-level kind (coarse_setup)
   int group;
 };
 template <int ND, int NRES, int G>
-Launchers launchers(bool sgs) {
-  return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>, sgs ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>, G};
+Launchers launchers(int kind) {
+  return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>,
+                   kind == C8_PRECOND_TWO_LEVEL ? launch_iteration_two_level<ND, NRES, G>
+                   : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>,
+                   coarse_setup<ND, NRES, G>, G};
 }
 
 int read_scalars(Solve const& q, KryScalars* h) {
@@ -996,12 +1038,16 @@ int build_colors(c8_ctx* c) {
 template <int ND, int NRES, int G>
 int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level;
   Solve q{};
   q.c = c;
   q.nn = c->mesh.nnodes;
   int const nown = c->halo ? c8_halo_num_owned(c->halo) : q.nn;
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_precondition: empty mesh");
+  if (two_level) {
+    int const rcc = coarse_refusals(c, "c8_krylov_precondition");
+    if (rcc != C8_OK) return rcc;
+  }
   if (nown <= 0) return C8_OK;
   size_t const n0 = (size_t)q.nn * ND, nu = (size_t)nown * ND, np_ = NRES == 2 ? (size_t)nown : (size_t)0;
   q.n = n0 + (NRES == 2 ? (size_t)q.nn : 0);
@@ -1037,10 +1083,12 @@ int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], doub
     return fail(C8_ERR_ARG, "c8_krylov_precondition: the diagonal block of node " + std::to_string(h.bad_node) +
                             " is singular or not finite (node-block Jacobi preconditioner)");
   if (!std::isfinite(h.rr)) return fail(C8_ERR_ARG, "c8_krylov_precondition: the vector or the matrix is not finite");
+  if (two_level && (rc = coarse_setup<ND, NRES, G>(q, true)) != C8_OK) return rc;
   if (sgs) {
     hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
-    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat)));
+    if (two_level) C8_HIP((launch_coarse<ND, NRES>(q, q.s, q.shat)));
+    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, !two_level)));
   } else {
     hipLaunchKernelGGL((k_prec_own<ND, NRES, 1>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nn, q.nb_node, q.minv, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
@@ -1077,11 +1125,11 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level;
   Launchers L;
-  if (c->ndims == 3 && two) L = launchers<3, 2, 16>(sgs);
-  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>(sgs);
-  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>(sgs);
+  if (c->ndims == 3 && two) L = launchers<3, 2, 16>(c->kry_precond);
+  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>(c->kry_precond);
+  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>(c->kry_precond);
   else {
     if (info) info->status = C8_ERR_UNSUPPORTED;
     return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: no kernels for this number of dimensions and residuals");
@@ -1098,6 +1146,10 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   q.nb_upd = (int)std::min<size_t>((q.n + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve: empty mesh");
   int rc;
+  if (two_level && (rc = coarse_refusals(c, "c8_krylov_solve")) != C8_OK) {
+    if (info) info->status = rc;
+    return rc;
+  }
   if (sgs && (rc = build_colors(c)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * nb * nb)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n)) != C8_OK) return rc;
@@ -1137,6 +1189,7 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   }
   double const tol = std::max(rel_tol * b_norm, abs_tol);
   q.tol2 = tol * tol;
+  if (two_level && (rc = L.coarse(q, true)) != C8_OK) return rc;  // A_c = P^T A P and its inverse for this matrix
 
   int restarts = 0, status = C8_NOT_CONVERGED;
   double true_norm = b_norm;
@@ -1194,6 +1247,7 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
+  if (c->kry_precond == C8_PRECOND_TWO_LEVEL) return coarse_refusals(c, "c8_krylov_solve_parts");  // (a halo is attached: refused)
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
   PartsLaunchers L;
   if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(sgs);
@@ -1323,7 +1377,7 @@ int c8_krylov_part_lists(c8_ctx* c, int32_t* num_interior, int32_t* num_boundary
 int c8_krylov_set_preconditioner(c8_ctx* c, int kind, int sweeps) {
   if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: null context");
   if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: a staged assembly is waiting for c8_gather_finish");
-  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS)
+  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL)
     return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: unknown preconditioner " + std::to_string(kind));
   c->kry_precond = kind;
   c->kry_sweeps = sweeps > 0 ? sweeps : 1;
@@ -1345,6 +1399,42 @@ int c8_krylov_colors(c8_ctx* c, int32_t* num_colors, const int32_t** color_ptr, 
   return C8_OK;
 }
 
+int c8_krylov_aggregates(c8_ctx* c, int32_t* num_aggregates, const int32_t** aggregate_of_node) {
+  if (!c || !num_aggregates || !aggregate_of_node) return fail(C8_ERR_ARG, "c8_krylov_aggregates: null argument");
+  if (c->halo) return coarse_refusals(c, "c8_krylov_aggregates");
+  if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_aggregates: empty mesh");
+  int const rc = build_aggregates(c);  // (reported above the cap of the coarse solve too)
+  if (rc != C8_OK) return rc;
+  *num_aggregates = c->kry_nagg;
+  *aggregate_of_node = c->kry_agg_of.data();
+  return C8_OK;
+}
+
+int c8_krylov_coarse_matrix(c8_ctx* c, const c8_system* sys, int32_t* n_coarse, double* out_host) {
+  if (!c || !sys || !n_coarse) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null argument");
+  bool const two = c->nres == 2;
+  if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
+    return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null array in the system");
+  int rc = coarse_refusals(c, "c8_krylov_coarse_matrix");
+  if (rc != C8_OK) return rc;
+  int const n = c->kry_nagg * coarse_columns(c), lda = (n + 1) & ~1;
+  *n_coarse = n;
+  if (!out_host) return C8_OK;
+  Solve q{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  if (c->ndims == 3 && two) rc = coarse_setup<3, 2, 16>(q, false);
+  else if (c->ndims == 2 && two) rc = coarse_setup<2, 2, 8>(q, false);
+  else if (c->ndims == 2 && !two) rc = coarse_setup<2, 1, 8>(q, false);
+  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_coarse_matrix: no kernels for this number of dimensions and residuals");
+  if (rc != C8_OK) return rc;
+  C8_HIP(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
+                          hipMemcpyDeviceToHost, c->stream));
+  C8_HIP(hipStreamSynchronize(c->stream));
+  return C8_OK;
+}
+
 int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   if (!c || !sys || !v || !y) return fail(C8_ERR_ARG, "c8_krylov_precondition: null argument");
   bool const two = c->nres == 2;
@@ -1357,3 +1447,8 @@ int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const 
 }
 
 }  // extern "C"
+
+void c8_krylov_release(c8_ctx* c) {
+  if (c->kry_rocblas) (void)rocblas_destroy_handle((rocblas_handle)c->kry_rocblas);
+  c->kry_rocblas = nullptr;
+}

@@ -10,7 +10,7 @@ C8_OK, C8_LOCAL_SOLVE_FAILED, C8_ERR_ARG, C8_ERR_DEVICE, C8_ERR_UNSUPPORTED, C8_
 C8_SCATTER_ATOMIC, C8_SCATTER_COLORED, C8_SCATTER_GATHER = 0, 1, 2
 C8_KERNEL_AUTO, C8_KERNEL_SLOT, C8_KERNEL_WAVE, C8_KERNEL_WAVE_AD, C8_KERNEL_NODE = 0, 1, 2, 3, 4
 C8_SCALE_NONE, C8_SCALE_LOG, C8_SCALE_BOUNDS = 0, 1, 2
-C8_PRECOND_BLOCK_JACOBI, C8_PRECOND_BLOCK_SGS = 0, 1
+C8_PRECOND_BLOCK_JACOBI, C8_PRECOND_BLOCK_SGS, C8_PRECOND_TWO_LEVEL = 0, 1, 3  # (2 is not a kind: refused)
 
 dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
@@ -185,6 +185,8 @@ SYMBOLS = [
     ("c8_krylov_set_preconditioner", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("c8_krylov_get_preconditioner", C.c_int, [C.c_void_p]),
     ("c8_krylov_colors", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p), C.POINTER(i32p)]),
+    ("c8_krylov_aggregates", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p)]),
+    ("c8_krylov_coarse_matrix", C.c_int, [C.c_void_p, C.POINTER(System), i32p, dp]),
     ("c8_krylov_precondition", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("c8_transform_params", C.c_int, [C.c_int, dp, i32p, dp, dp, C.c_int, dp]),
     ("c8_transform_gradient", C.c_int, [C.c_int, dp, dp, i32p, dp, dp, dp]),

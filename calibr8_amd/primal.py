@@ -74,7 +74,9 @@ class DeviceSolver:
 
 def device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditioner="jacobi", sweeps=1, **opts):
     """Linear solve on the device: right-preconditioned BiCGStab (c8_krylov_solve) with node-block Jacobi, or with
-    preconditioner="sgs" `sweeps` symmetric multicolour node-block Gauss-Seidel sweeps.  The preconditioner is state of the
+    preconditioner="sgs" `sweeps` symmetric multicolour node-block Gauss-Seidel sweeps, or with preconditioner="two_level" a
+    coarse correction over node aggregates ahead of those sweeps (C8_PRECOND_TWO_LEVEL: dense coarse solve, refused above
+    8192 coarse unknowns).  The preconditioner is state of the
     assembler's context: this call SETS it (Assembler.set_krylov_preconditioner, refused while a staged assembly waits for
     gather_finish), the default "jacobi" included, so it overrides an earlier choice and holds for every solver on `asm`.
     Usable wherever `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem,

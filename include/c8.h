@@ -371,10 +371,12 @@ int c8_adjoint_solve_step(c8_ctx* ctx, const c8_state* st, const c8_system* sys,
  * diagonal block over its equations (u and p of the node: 4 x 4, 3 x 3 on tri3 meshes, 2 x 2 under
  * mechanics_plane_stress).  Everything stays in HBM on the context's stream; the host reads the residual norm every
  * `check_every` iterations.  No floating-point atomics: the same inputs give the same bits.  This stands in for the
- * reference's Belos / Teko / MueLu stack on one part; it is no multigrid (iteration counts grow like 1 / h).
+ * reference's Belos / Teko / MueLu stack on one part.  With block Jacobi the iteration counts grow like 1 / h.
  * c8_krylov_set_preconditioner below selects multicolour node-block symmetric Gauss-Seidel instead: several times fewer
- * iterations at about three times the matrix traffic per iteration, the same growth with 1 / h (one level, no coarse
- * space), the same reproducibility. */
+ * iterations at about three times the matrix traffic per iteration, the same growth with 1 / h, the same
+ * reproducibility; or C8_PRECOND_TWO_LEVEL, which adds a coarse space of rigid-body modes per aggregate of nodes:
+ * two levels, dense coarse solve, capped at 8192 coarse unknowns (meshes up to roughly 10^5 nodes).  It is no
+ * multilevel method: a recursive coarse solve is what would lift that cap. */
 typedef struct {
   int32_t max_iters;      /* iterations (two A x each); default 20000 when <= 0 */
   int32_t check_every;    /* host reads the residual norm every this many iterations; default 10 */
@@ -437,14 +439,51 @@ int c8_krylov_part_lists(c8_ctx* ctx, int32_t* num_interior, int32_t* num_bounda
  *   parts     with a halo attached only the owned nodes are coloured (over the owned sub-graph) and columns with local id
  *             >= num_owned are skipped: a part-local (hybrid) Gauss-Seidel, no message inside the preconditioner
  * Nodes of one colour do not couple: the apply has no floating-point atomics and is a pure function of its inputs.
- * An unknown kind, or a call while a staged assembly waits for c8_gather_finish, returns C8_ERR_ARG. */
+ * An unknown kind, or a call while a staged assembly waits for c8_gather_finish, returns C8_ERR_ARG.
+ *
+ * C8_PRECOND_TWO_LEVEL is a coarse correction followed by `sweeps` of those symmetric sweeps (sweeps <= 0: one).  One part
+ * only: with a halo attached c8_krylov_solve_parts, c8_krylov_precondition, c8_krylov_aggregates and
+ * c8_krylov_coarse_matrix return C8_ERR_UNSUPPORTED while this kind is selected (one rank included).
+ *   aggregates   on the host, over the node graph.  Pass 1, nodes in ascending id: a node whose whole graph row (itself
+ *             included) is still unaggregated opens a new aggregate holding that row.  Pass 2, ascending id: a node still
+ *             free joins the pass-1 aggregate of its lowest-id neighbour that pass 1 aggregated.  Pass 3, ascending id: a
+ *             node still free becomes an aggregate of its own.  Aggregate ids are in order of creation.
+ *   P         every aggregate carries the rigid-body modes about its centroid (the mean of its nodes' coordinates, summed in
+ *             ascending id) and a constant pressure where there is a p equation.  3-D mechanics, 7 columns: 3 translations,
+ *             3 rotations e_m x (x_i - centroid), constant p; tri3 mechanics, 4 columns: 2 translations, the rotation
+ *             (-(y - ybar), x - xbar), constant p; mechanics_plane_stress, 3 columns.  Columns in this order,
+ *             aggregate-major.  An equation row of A is CONSTRAINED when every off-diagonal entry of the row is exactly 0
+ *             in all blocks (the rows c8_apply_dirichlet leaves; found on the device at every set-up): its row of P is zero.
+ *   A_c       = P^T A P, formed on the device at every solve, dense, then inverted (LU with partial pivoting, rocSOLVER).  A
+ *             column of P that is zero (every row of a mode constrained; the rotations of a one-node aggregate) gets a
+ *             unit diagonal.  n_coarse = aggregates x columns must not exceed 8192 (a 512 MB inverse): above it the solve
+ *             and the apply return C8_ERR_UNSUPPORTED, the message names n_coarse and the cap, nothing is iterated.  That
+ *             makes this kind a method for meshes up to roughly 10^5 nodes; a recursive (multilevel) coarse solve is what
+ *             lifts the cap.  A_c singular or not finite: C8_ERR_ARG, the message names the aggregate.
+ *   y = M^-1 v   x = P A_c^-1 P^T v, then the symmetric sweeps above started from this x instead of 0 (every colour launch
+ *             reads the whole graph row); y = x.  A fixed linear operator: BiCGStab stays valid.
+ * Reproducibility: every kernel of this library in the set-up and in the apply sums in a fixed order without
+ * floating-point atomics, so A_c, and everything downstream of a given inverse, are pure functions of their inputs.  The
+ * inverse itself comes from rocSOLVER (dgetrf, dgetri), which this library does not control; on the library versions it was
+ * tested with, repeated solves in one process and in a fresh process gave the same bits (tests/test_gpu_krylov_two_level.py
+ * asserts it). */
 enum { C8_PRECOND_BLOCK_JACOBI = 0, C8_PRECOND_BLOCK_SGS = 1 };
+enum { C8_PRECOND_TWO_LEVEL = 3 };  /* 2 stays unassigned: callers have been told since the Gauss-Seidel kind that
+                                       2 is refused as an unknown kind, and it still is */
 int c8_krylov_set_preconditioner(c8_ctx* ctx, int kind, int sweeps);
 int c8_krylov_get_preconditioner(const c8_ctx* ctx);  /* C8_PRECOND_* (C8_ERR_ARG for a null context) */
 /* Diagnostic / test access: the colour lists of the Gauss-Seidel sweeps (HOST arrays owned by the context, built at the
  * first use, rebuilt when a halo has been attached since): nodes[color_ptr[c] .. color_ptr[c + 1]) are the nodes of
  * colour c, ascending.  With a halo attached only the owned nodes are listed. */
 int c8_krylov_colors(c8_ctx* ctx, int32_t* num_colors, const int32_t** color_ptr, const int32_t** nodes);
+/* Diagnostic / test access: the aggregates of C8_PRECOND_TWO_LEVEL (HOST array owned by the context, built at the first
+ * use, freed by c8_destroy): aggregate_of_node[i] in [0, num_aggregates) for every node i.  Reported above the cap of the
+ * coarse solve too.  C8_ERR_UNSUPPORTED with a halo attached. */
+int c8_krylov_aggregates(c8_ctx* ctx, int32_t* num_aggregates, const int32_t** aggregate_of_node);
+/* Diagnostic / test access: runs the set-up of C8_PRECOND_TWO_LEVEL on `sys` up to A_c = P^T A P (whatever kind is
+ * selected) and copies the dense row-major n_coarse x n_coarse matrix to out_host (HOST memory); out_host NULL returns
+ * n_coarse only.  C8_ERR_UNSUPPORTED with a halo attached or above the cap. */
+int c8_krylov_coarse_matrix(c8_ctx* ctx, const c8_system* sys, int32_t* n_coarse, double* out_host);
 /* y = M^-1 v, once, with the context's current preconditioner: the block inverses and the kernels of the solve, and its
  * refusals (C8_ERR_ARG for a singular diagonal block, the node named, and for a vector or matrix that is not finite).
  * v and y are DEVICE pointers laid out as b and dx (v[1], y[1] unused when c8_num_residuals() == 1).  Not collective: with
