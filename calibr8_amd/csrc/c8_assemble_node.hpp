@@ -13,15 +13,22 @@
 // the shape functions -- the bulk of the arithmetic -- is split over the nodes without redundancy: every 4 x 4
 // block of the element matrix is formed exactly once, by the wavefront of its row node.
 //
+//   top      lane = (point, node)   forward assembly: the 64 shape values of the reference element at its points into LDS
+//            (nshape): they are the same for every element, phases A and B read them instead of forming them at every step
 //   phase A  lane = (element s of the node, point)      interpolate the point quantities from the element's nodal
 //            values and cached shape tables, closed form (radial return, consistent tangent), the row node's record of
 //            the point into LDS, the point's share of the node's residual; the lane of the element's local node 0
 //            stores the converged local state
 //   phase B  lane = (element s of the node, column node m)   the 4 x 4 block d R_(node,.) / d x_(m,.) summed over the
 //            element's eight points: 16 accumulators
-//   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order
-//            (acc[position of the column node in the node's graph row][16])
-//   phase D  the finished rows added to (or assigned to) the four CSR blocks, the residual entries to b
+//   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order.  The
+//            accumulator is an IMAGE of the node's four CSR row blocks, entry for entry in their order (NodeShared::img*)
+//   phase D  the finished rows added to (or assigned to) the four CSR blocks -- four straight copies, lane j + 64 it
+//            takes entry j + 64 it of a block -- the residual entries to b
+//
+// In the walks over the skewed shape table (phases A and B) a lane keeps ONE rotating byte offset, (off + 8) & 56, and
+// derives every address of a step from it by a shift: the table's two columns, the nodal values, the record, nshape.
+// (With nshape in place this saves 7 vector instructions per node and costs 4 registers: no measurable time either way.)
 //
 // Requires an element with 8 nodes, 8 coupled points and identical point sets for both ip sets (hex8), the cached
 // shape tables (c8_set_shape_cache) and xi != xi_prev (an element's previous state is read by eight wavefronts).
@@ -44,6 +51,12 @@ template <class M> struct has_closed_form_rows<M, std::enable_if_t<M::HAS_CLOSED
 // MANY = false (every node of the mesh has at most eight elements): the row accumulator takes the place of the point
 // records once phase B has read them; MANY = true: a node's elements go through phases A-C eight at a time and the
 // accumulator has its own storage.
+// The accumulator of a node of degree deg is the image of its four CSR row blocks, 16 deg doubles, entry (row i, position
+// pos of the column node in the node's graph row, column col) where the CSR block has it:
+//   img00 [i * 3 deg + 3 pos + col]  (u_i, u_col)   9 deg     img01 [i * deg + pos]  (u_i, p)   3 deg
+//   img10 [3 pos + col]              (p, u_col)     3 deg     img11 [pos]            (p, p)       deg
+// Within one ds_add_f64 of phase C the lanes' addresses are 3 or 1 doubles apart per position: 16 consecutive positions
+// meet in 16 different bank pairs.
 template <class E, class ModelD, int MAXDEG, bool MANY> struct NodeShared {
   static constexpr int NR = ModelD::NROW;
   // record + the point's four residual shares.  Even (16-byte LDS reads) and such that the records of two elements lie
@@ -51,15 +64,22 @@ template <class E, class ModelD, int MAXDEG, bool MANY> struct NodeShared {
   // 16-lane LDS access then never meet in a bank
   static constexpr int LDR = NR + 4;
   static_assert(LDR % 2 == 0 && (E::NP0 * LDR * 8) % 256 == 128, "record stride: 16-byte aligned, element groups 32 banks apart");
-  static constexpr int LDA = 18;            // accumulator row: 16 entries + padding, 16-byte aligned
-  static constexpr int NREC = 8 * E::NP0 * LDR, NACC = MAXDEG * LDA;
+  static constexpr int NREC = 8 * E::NP0 * LDR, NACC = MAXDEG * 16;
   alignas(16) double buf[MANY ? NREC + NACC : (NREC > NACC ? NREC : NACC)];
   alignas(16) double nodal[8][E::NN][4];    // (u_0, u_1, u_2, p) of the nodes of the eight elements, loaded one node per lane
+  double nshape[E::NP0][E::NN];             // N_n at point pt of the reference element: HexShape::of_point(pt).at_node(n)
+                                            // (forward assembly; the struct has no ADJ parameter, the adjoint leaves it unused)
   double el[8][2];                          // per element: the model's per-element scalars (closed_form_row)
   double bsum[4];
   C8_HD double* rec(int s, int pt) { return buf + (s * E::NP0 + pt) * LDR; }
-  C8_HD double* acc(int pos) { return buf + (MANY ? NREC : 0) + pos * LDA; }
+  C8_HD double* img() { return buf + (MANY ? NREC : 0); }  // img00 starts here, the others at:
+  C8_HD static int img01(int deg) { return 9 * deg; }
+  C8_HD static int img10(int deg) { return 12 * deg; }
+  C8_HD static int img11(int deg) { return 15 * deg; }
 };
+
+// the double at BYTE offset off (a multiple of 8) from p
+C8_HD double const* at_byte(double const* p, int off) { return reinterpret_cast<double const*>(reinterpret_cast<char const*>(p) + off); }
 
 #ifndef C8_TUNE_NODE_HAHEAD
 #define C8_TUNE_NODE_HAHEAD 3
@@ -77,7 +97,12 @@ template <int MAXDEG> struct NodeLane {
 
 // shape values of the reference hex8 at its Gauss points: E::N(n, xi) operation for operation, 0.125 (1 + sx xi_0)
 // (1 + sy xi_1) (1 + sz xi_2), with either the point (of_point) or the node (of_node) fixed per lane and the other index a
-// compile-time constant or a lane value; signs are selected as values (no indexed tables: they would live in scratch)
+// lane value; signs are selected as values (no indexed tables: they would live in scratch).
+// Forward assembly: evaluated once per wavefront, one (point, node) pair per lane, into NodeShared::nshape.  One table
+// serves the lanes that own a point and walk the nodes (phase A) and those that own a node and walk the points (phase B):
+// the signs are +-1, so 1 + s * xi is exact in the product whichever index is fixed, and the factors are multiplied in the
+// same order -- at_node and at_point give the same bits.  Adjoint assembly: formed at every step as before; with the table
+// K3 measured 2.5-3.4 % SLOWER.
 template <class E> struct HexShape {
   double c[3];  // of_point: the point's coordinates; of_node: the node's signs
   C8_HD static HexShape of_point(int pt) {
@@ -125,14 +150,19 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
   C8_NSTAMP(0);
   auto zero_acc = [&](int lane) {
     C8_UNROLL
-    for (int it = 0; it < (MAXDEG * SH::LDA + 63) / 64; ++it) {
+    for (int it = 0; it < (SH::NACC + 63) / 64; ++it) {
       int const q = lane + 64 * it;
-      if (q < deg * SH::LDA) sh.acc(0)[q] = 0.;
+      if (q < 16 * deg) sh.img()[q] = 0.;
     }
     if (lane < 4) sh.bsum[lane] = 0.;
   };
-  if (MANY) {
-    ex.each([&](int lane) { zero_acc(lane); });
+  // forward assembly: the reference element's shape values, lane = (point, node).  Here and not in the kernel's wrapper: the
+  // function is the unit the CPU emulation calls
+  if (!ADJ || MANY) {
+    ex.each([&](int lane) {
+      if (!ADJ) sh.nshape[lane >> 3][lane & 7] = HexShape<E>::of_point(lane >> 3).at_node(lane & 7);
+      if (MANY) zero_acc(lane);
+    });
     ex.sync();
   }
   for (int c0 = e0; c0 < e1; c0 += 8) {  // eight elements of the node at a time (MANY = false: exactly one round)
@@ -162,12 +192,14 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     ex.each([&](int lane_) {
       auto& r = ex.lane(lane_);
       int lane = lane_;
-      C8_PIN(lane);  // the shape values below are formed here, not at the top of the kernel and kept in registers
+      C8_PIN(lane);  // the offsets below are formed here, not at the top of the kernel and kept in registers
       int const s = lane >> 3, pt = lane & 7;
       if (!r.valid) return;
       int const e = r.e, a = r.a;
       double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
-      HexShape<E> const Np = HexShape<E>::of_point(pt);
+      double const* const Np = sh.nshape[pt];                  // this point's shape values: forward, from the table;
+      HexShape<E> NpH;                                         // adjoint, formed per step
+      if constexpr (ADJ) NpH = HexShape<E>::of_point(pt);
       // adjoint assembly: this point's history entries (f at the node's four rows, g), fetched under the interpolation
       double fh4[4] = {0., 0., 0., 0.}, gx[NL];
       C8_UNROLL
@@ -180,7 +212,9 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       }
       // interpolation (global_residual.cpp:289-332).  The table is skewed (shape_dn_offset): at step i the element's eight
       // lanes read row i, this lane the entry of node m = (i - pt) mod 8 -- the sum over the nodes starts at node -pt mod 8
-      // and wraps; the row node's own entry (g below) is kept when it comes by.  Four nodes' operands in flight at a time
+      // and wraps; the row node's own entry (g below) is kept when it comes by.  Four nodes' operands in flight at a time.
+      // off = 8 m, the byte offset of node m in a row of eight doubles, rotates from step to step; shifted, it addresses the
+      // row's 16-byte column, its 8-byte column, the node's values in sh.nodal and its shape value
       double q[WQ];
       C8_UNROLL
       for (int c = 0; c < WQ; ++c) q[c] = 0.;
@@ -188,18 +222,22 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
 #define C8_TUNE_NODE_GSEL 0
 #endif
       double g[3] = {0., 0., 0.};
+      int off = ((0 - pt) & 7) * 8;
       C8_UNROLL
       for (int i = 0; i < E::NN; ++i) {
-        int const m = (i - pt) & 7;
         double const* const row = t + i * 24;
-        double const d0 = row[m * 2 + 0], d1 = row[m * 2 + 1], d2 = row[16 + m];
+        double const* const d01 = at_byte(row, 2 * off);
+        double const d0 = d01[0], d1 = d01[1], d2 = *at_byte(row + 16, off);
         if (C8_TUNE_NODE_GSEL) {
-          bool const own = m == a;
+          bool const own = off == 8 * a;
           g[0] = own ? d0 : g[0]; g[1] = own ? d1 : g[1]; g[2] = own ? d2 : g[2];
         }
-        double const Nm = Np.at_node(m);
-        double const* const nv = sh.nodal[s][m];
+        double Nm;
+        if constexpr (ADJ) Nm = NpH.at_node(off >> 3);
+        else Nm = *at_byte(Np, off);
+        double const* const nv = at_byte(sh.nodal[s][0], 4 * off);
         double const u0 = nv[0], u1 = nv[1], u2 = nv[2], pm = nv[3];
+        off = (off + 8) & 56;
         q[0] += u0 * d0; q[1] += u0 * d1; q[2] += u0 * d2;
         q[3] += u1 * d0; q[4] += u1 * d1; q[5] += u1 * d2;
         q[6] += u2 * d0; q[7] += u2 * d1; q[8] += u2 * d2;
@@ -233,7 +271,9 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       C8_NSTAMP(8);
       double const w = t[SHAPE_WDV + pt];
       if (!C8_TUNE_NODE_GSEL) { g[0] = t[shape_dn_offset(pt, a, 0)]; g[1] = t[shape_dn_offset(pt, a, 1)]; g[2] = t[shape_dn_offset(pt, a, 2)]; }
-      double const Na = Np.at_node(a);
+      double Na;
+      if constexpr (ADJ) Na = NpH.at_node(a);
+      else Na = Np[a];
       double* const rc = sh.rec(s, pt);
       double el[2];
       Model::template closed_form_row<ADJ>(cf.t, w, g, Na, rc, el);
@@ -277,18 +317,20 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       if (!r.valid) return;
       int const s = lane >> 3, m = lane & 7;
       double const* const t = mt.shape + (size_t)r.e * SHAPE_STRIDE;
-      HexShape<E> const Nn = HexShape<E>::of_node(m);
       double const el[2] = {sh.el[s][0], sh.el[s][1]};
+      HexShape<E> Nn;  // adjoint only
+      if constexpr (ADJ) Nn = HexShape<E>::of_node(m);
       // dN_m/dx of this lane's column node: at step i the element's eight lanes read row i of the skewed table, this lane
       // the entry of point (i - m) mod 8; C8_TUNE_NODE_HAHEAD steps ahead of the arithmetic (the element's table is in L1 /
-      // L2 by now)
+      // L2 by now).  off = 8 pt rotates from step to step; multiplied, it addresses the point's record and the node's shape
+      // value at the point
       constexpr int AH = C8_TUNE_NODE_HAHEAD;
       double hq[AH + 1][3];
       C8_UNROLL
       for (int k = 0; k < AH; ++k) { hq[k][0] = t[k * 24 + m * 2 + 0]; hq[k][1] = t[k * 24 + m * 2 + 1]; hq[k][2] = t[k * 24 + 16 + m]; }
+      int off = ((0 - m) & 7) * 8;
       C8_UNROLL
       for (int i = 0; i < E::NP0; ++i) {
-        int const pt = (i - m) & 7;
         hq[AH][0] = hq[AH][1] = hq[AH][2] = 0.;
         if (i + AH < E::NP0) {
           hq[AH][0] = t[(i + AH) * 24 + m * 2 + 0];
@@ -296,7 +338,11 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
           hq[AH][2] = t[(i + AH) * 24 + 16 + m];
         }
         double const hc[3] = {hq[0][0], hq[0][1], hq[0][2]};
-        Model::closed_form_block(sh.rec(s, pt), el, hc, Nn.at_point(pt), r.J);
+        double Nm;
+        if constexpr (ADJ) Nm = Nn.at_point(off >> 3);
+        else Nm = *at_byte(&sh.nshape[0][m], E::NN * off);
+        Model::closed_form_block(at_byte(sh.rec(s, 0), SH::LDR * off), el, hc, Nm, r.J);
+        off = (off + 8) & 56;
         // one point's record in registers at a time: without the lines below the compiler fetches the records of all
         // eight points first (over a hundred doubles) and spills
         C8_UNROLL
@@ -347,28 +393,34 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     C8_NSTAMP(3);
     // ---- phase C: the elements' blocks into the row accumulator (ds_add_f64), the sums into one entry taken in ascending
     //      element order --------------------------------------------------------------------------------------------
+    // A lane forms its few base addresses once from pos, deg and n3; the sixteen adds keep the order of the block's entries
+    auto add_block = [&](int lane) {
+      auto& r = ex.lane(lane);
+      double* const c00 = sh.img() + 3 * r.pos;                // (u_0, u_.) of this column node; rows u_1, u_2 follow n3 apart
+      double* const c01 = sh.img() + SH::img01(deg) + r.pos;   // (u_0, p); rows u_1, u_2 follow deg apart
+      double* const c10 = sh.img() + SH::img10(deg) + 3 * r.pos;
+      double* const c11 = sh.img() + SH::img11(deg) + r.pos;
+      C8_UNROLL
+      for (int j = 0; j < 16; ++j) {
+        int const i = j >> 2, col = j & 3;
+        ex.lds_add(i < 3 ? (col < 3 ? c00 + i * n3 + col : c01 + i * deg) : (col < 3 ? c10 + col : c11), r.J[j]);
+      }
+      if ((lane & 7) < 4) ex.lds_add(&sh.bsum[lane & 7], r.rs);
+    };
 #ifndef C8_TUNE_NODE_C_BY_ELEMENT
     // all elements in one pass.  Lanes of one instruction that add to the same entry (a column node shared by several of the
     // node's elements) are served by the LDS unit in ascending lane order, i.e. in ascending element order: the results are
     // bitwise those of the element-by-element form below (measured on jiggled meshes, forward and adjoint, tools/README.md),
     // which took eight times the LDS instructions (K1 4.68 -> 4.46 ms)
     ex.each([&](int lane) {
-      auto& r = ex.lane(lane);
       if ((lane >> 3) >= ne) return;
-      double* const ac = sh.acc(r.pos);
-      C8_UNROLL
-      for (int j = 0; j < 16; ++j) ex.lds_add(ac + j, r.J[j]);
-      if ((lane & 7) < 4) ex.lds_add(&sh.bsum[lane & 7], r.rs);
+      add_block(lane);
     });
 #else  // one element after the other: within one element the column nodes are distinct and so are the addresses
     for (int s2 = 0; s2 < ne; ++s2) {
       ex.each([&](int lane) {
-        auto& r = ex.lane(lane);
         if ((lane >> 3) != s2) return;
-        double* const ac = sh.acc(r.pos);
-        C8_UNROLL
-        for (int j = 0; j < 16; ++j) ex.lds_add(ac + j, r.J[j]);
-        if ((lane & 7) < 4) ex.lds_add(&sh.bsum[lane & 7], r.rs);
+        add_block(lane);
       });
     }
 #endif
@@ -389,25 +441,22 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     for (int it = 0; it < NL_::N01; ++it) { C8_PIN(r.a01[it]); C8_PIN(r.a10[it]); }
     C8_PIN(r.a11);
     C8_PIN(r.bold);
+    // the image is in the blocks' own order: entry j of a block is entry j of its image
+    double const* const i00 = sh.img(), * const i01 = i00 + SH::img01(deg), * const i10 = i00 + SH::img10(deg), * const i11 = i00 + SH::img11(deg);
     C8_UNROLL
     for (int it = 0; it < NL_::N00; ++it) {
       int const j = lane + 64 * it;
-      if (j < 9 * deg) {
-        int const i = (j >= n3) + (j >= 2 * n3), jj = j - i * n3, pos = jj / 3, col = jj - 3 * pos;
-        ga.A[0][0][np * 9 + j] = r.a00[it] + sh.acc(pos)[i * 4 + col];
-      }
+      if (j < 9 * deg) ga.A[0][0][np * 9 + j] = r.a00[it] + i00[j];
     }
     C8_UNROLL
     for (int it = 0; it < NL_::N01; ++it) {
       int const j = lane + 64 * it;
       if (j < n3) {
-        int const i = (j >= deg) + (j >= 2 * deg), pos = j - i * deg;
-        ga.A[0][1][np * 3 + j] = r.a01[it] + sh.acc(pos)[i * 4 + 3];
-        int const pos2 = j / 3, col = j - 3 * pos2;
-        ga.A[1][0][np * 3 + j] = r.a10[it] + sh.acc(pos2)[3 * 4 + col];
+        ga.A[0][1][np * 3 + j] = r.a01[it] + i01[j];
+        ga.A[1][0][np * 3 + j] = r.a10[it] + i10[j];
       }
     }
-    if (lane < deg) ga.A[1][1][np + lane] = r.a11 + sh.acc(lane)[15];
+    if (lane < deg) ga.A[1][1][np + lane] = r.a11 + i11[lane];
     if (lane < 3) ga.b[0][(size_t)node * 3 + lane] = r.bold + sh.bsum[lane];
     if (lane == 3) ga.b[1][node] = r.bold + sh.bsum[3];
   });
