@@ -200,15 +200,25 @@ class Assembler:
     def set_krylov_preconditioner(self, kind, sweeps=1):
         """Preconditioner of the device solves on this assembler: "jacobi" (node-block Jacobi, the default), "sgs"
         (`sweeps` symmetric multicolour node-block Gauss-Seidel sweeps) or "two_level" (a coarse correction with the
-        rigid-body modes of node aggregates, then `sweeps` of those sweeps; one part only); c8_krylov_set_preconditioner."""
-        kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS, "two_level": _l.C8_PRECOND_TWO_LEVEL}
+        rigid-body modes of node aggregates, then `sweeps` of those sweeps; one part only) or "multilevel" (the same
+        construction repeated on the coarse matrix, `sweeps` per level, set_krylov_multilevel; one part only);
+        c8_krylov_set_preconditioner."""
+        kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS, "two_level": _l.C8_PRECOND_TWO_LEVEL,
+                 "multilevel": _l.C8_PRECOND_MULTILEVEL}
         if kind not in kinds:
-            raise ValueError("preconditioner must be 'jacobi', 'sgs' or 'two_level', not %r" % (kind,))
+            raise ValueError("preconditioner must be 'jacobi', 'sgs', 'two_level' or 'multilevel', not %r" % (kind,))
         _l.check(self.L.c8_krylov_set_preconditioner(self.h, kinds[kind], int(sweeps)))
 
     @property
     def krylov_preconditioner(self):
-        return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs", _l.C8_PRECOND_TWO_LEVEL: "two_level"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
+        return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs", _l.C8_PRECOND_TWO_LEVEL: "two_level",
+                _l.C8_PRECOND_MULTILEVEL: "multilevel"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
+
+    def set_krylov_multilevel(self, coarse_max=None, max_levels=None):
+        """Settings of the "multilevel" preconditioner: another level is built while the coarsest one has more than
+        `coarse_max` unknowns and fewer than `max_levels` levels exist (the system counts as one); None: the library's
+        default.  The levels are rebuilt at the next solve; c8_krylov_set_multilevel."""
+        _l.check(self.L.c8_krylov_set_multilevel(self.h, int(coarse_max or 0), int(max_levels or 0)))
 
     def set_assign_mode(self, on):
         """scatter='gather': Jacobian assemblies assign A and b (zero_all + assembly in one call) instead of adding"""

@@ -13,6 +13,26 @@
 
 int c8_fail(int code, std::string const& msg);  // records c8_last_error() and returns code
 
+// a level l >= 1 of the multilevel preconditioner (c8_krylov_multilevel.hpp): one node per aggregate of the level above
+struct c8_kry_level {
+  int n = 0;                          // nodes
+  std::vector<int32_t> gp, ga;        // graph: the neighbour lists of the aggregates it came from (sorted, self included)
+  std::vector<double> x;              // [n][3] positions: the centroids of those aggregates
+  // ... what follows only where a level below exists (not on the last level, which is dense)
+  int nagg = 0, max_nbr = 0;          // aggregates of this level's nodes; most neighbouring aggregates of one of them
+  std::vector<int32_t> agg_of;        // [n]
+  std::vector<int32_t> color_ptr, color_nodes;  // colour lists of the level's sweeps (layout of kry_color_*)
+  int32_t* d_graph = nullptr;         // gp, then ga
+  int32_t* d_agg = nullptr;           // layout of c8_ctx::d_kry_agg
+  size_t agg_at[6] = {0, 0, 0, 0, 0, 0};
+  double* d_off = nullptr;            // [n][ndims] node - centroid of its aggregate
+  int32_t* d_flags = nullptr;         // [n] constrained-row flags of the current matrix
+  int32_t* d_colors = nullptr;        // device mirror of color_nodes
+  double* d_A = nullptr;              // [graph entries][NC * NC] block-sparse matrix of the level
+  double* d_minv = nullptr;           // [n][NC * NC] inverses of the diagonal blocks
+  double* d_vec = nullptr;            // right-hand side and iterate of the level, [n][NC] each
+};
+
 struct c8_ctx {
   // (namespace c8 types)
   c8::HostMesh mesh;
@@ -126,6 +146,13 @@ struct c8_ctx {
   int32_t* d_kry_ipiv = nullptr;     // pivots of the LU factorisation, then the three status words of the set-up
   size_t kry_Ac_n = 0, kry_cvec_n = 0, kry_ipiv_n = 0;
   void* kry_rocblas = nullptr;       // rocblas_handle of the dense inverse (workspace inside), made at first use
+  // ... the levels of C8_PRECOND_MULTILEVEL below level 0 (c8_krylov_multilevel.hpp), built at first use and again after
+  // c8_krylov_set_multilevel; level 1's graph and positions come with the aggregates above
+  std::vector<int32_t> kry_agg_nbr_ptr, kry_agg_nbr;  // neighbouring aggregates of every aggregate: the graph of level 1
+  std::vector<double> kry_agg_x;     // [kry_nagg][3] centroids
+  int kry_ml_coarse_max = 0, kry_ml_max_levels = 0;   // (set by c8_krylov.hip: <= 0 until the first use = the defaults)
+  bool kry_ml_built = false;
+  std::vector<c8_kry_level> kry_levels;               // [k] is level k + 1; freed by c8_krylov_release
 };
 void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)

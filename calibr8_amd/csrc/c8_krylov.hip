@@ -20,6 +20,8 @@
 // every other launch of the iteration is the same.  With C8_PRECOND_TWO_LEVEL the sweeps start from the coarse correction
 // x = P A_c^-1 P^T rhs instead of 0 (k_restrict, k_coarse_apply, k_prolong after k_vec; c8_krylov_coarse.hpp, DESIGN.md
 // section 13d), and the set-up of a solve forms A_c and its dense inverse.
+// With C8_PRECOND_MULTILEVEL the coarse correction is itself a recursion over further aggregated levels (c8_krylov_multilevel.hpp,
+// DESIGN.md section 13e): block-sparse coarse matrices with sweeps of their own, the dense inverse on the last level only.
 //
 // Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
 // the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
@@ -572,15 +574,20 @@ int launch_iteration_sgs(Solve const& q) {
   return C8_OK;
 }
 
-// launch_iteration_sgs with the sweeps started from the coarse correction of their right-hand side
-template <int ND, int NRES, int G>
+void color_graph(int n, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, std::vector<int32_t>* color_ptr,
+                 std::vector<int32_t>* color_nodes);
+#include "c8_krylov_multilevel.hpp"
+
+// launch_iteration_sgs with the sweeps started from the coarse correction of their right-hand side: of the two-level kind,
+// or of the multilevel one (MULTI)
+template <int ND, int NRES, int G, bool MULTI = false>
 int launch_iteration_two_level(Solve const& q) {
   hipStream_t const st = q.c->stream;
   int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
   size_t const n0 = (size_t)q.nn * ND;
   hipLaunchKernelGGL((k_vec<0>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.p, q.phat, q.S);
   C8_HIP(hipGetLastError());
-  C8_HIP((launch_coarse<ND, NRES>(q, q.p, q.phat)));
+  C8_HIP((MULTI ? launch_multilevel<ND, NRES>(q, q.p, q.phat) : launch_coarse<ND, NRES>(q, q.p, q.phat)));
   C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat, false)));
   hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
                      q.part, q.S);
@@ -589,7 +596,7 @@ int launch_iteration_two_level(Solve const& q) {
   C8_HIP(hipGetLastError());
   hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.s, q.shat, q.S);
   C8_HIP(hipGetLastError());
-  C8_HIP((launch_coarse<ND, NRES>(q, q.s, q.shat)));
+  C8_HIP((MULTI ? launch_multilevel<ND, NRES>(q, q.s, q.shat) : launch_coarse<ND, NRES>(q, q.s, q.shat)));
   C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat, false)));
   hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
                      q.part, q.S);
@@ -608,14 +615,16 @@ struct Launchers {
   int (*residual)(Solve const&);
   int (*iteration)(Solve const&);
   int (*coarse)(Solve const&, bool);  // the coarse level of the two-level kind (coarse_setup)
+  int (*levels)(Solve const&, int);   // the hierarchy of the multilevel kind (multilevel_setup)
   int group;
 };
 template <int ND, int NRES, int G>
 Launchers launchers(int kind) {
   return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>,
-                   kind == C8_PRECOND_TWO_LEVEL ? launch_iteration_two_level<ND, NRES, G>
+                   kind == C8_PRECOND_MULTILEVEL ? launch_iteration_two_level<ND, NRES, G, true>
+                   : kind == C8_PRECOND_TWO_LEVEL ? launch_iteration_two_level<ND, NRES, G>
                    : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>,
-                   coarse_setup<ND, NRES, G>, G};
+                   coarse_setup<ND, NRES, G>, multilevel_setup<ND, NRES, G>, G};
 }
 
 int read_scalars(Solve const& q, KryScalars* h) {
@@ -995,18 +1004,16 @@ int build_part_lists(c8_ctx* c) {
   return C8_OK;
 }
 
-// the colour lists of the Gauss-Seidel sweeps from the host graph (greedy, ascending node id, smallest free colour) and
-// their device mirror: all nodes, or the owned nodes over the owned sub-graph when a halo is attached
-int build_colors(c8_ctx* c) {
-  int const want = c->halo ? c8_halo_num_owned(c->halo) : -1;
-  if (c->kry_colors_for == want) return C8_OK;
-  int const n = c->halo ? want : c->mesh.nnodes;
+// greedy colouring of the first n nodes of a graph over their sub-graph: nodes in ascending id, each takes the smallest
+// colour no already-coloured neighbour has; nodes color_nodes[color_ptr[k] .. color_ptr[k + 1]) have colour k, ascending
+void color_graph(int n, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, std::vector<int32_t>* color_ptr,
+                 std::vector<int32_t>* color_nodes) {
   std::vector<int32_t> color(std::max(n, 0), -1), used;
   int nc = 0;
   for (int i = 0; i < n; ++i) {
     used.assign(nc + 1, 0);
-    for (int32_t k = c->graph.nodeptr[i]; k < c->graph.nodeptr[i + 1]; ++k) {
-      int32_t const j = c->graph.nodeadj[k];
+    for (int32_t k = gp[i]; k < gp[i + 1]; ++k) {
+      int32_t const j = ga[k];
       if (j < i && color[j] >= 0) used[color[j]] = 1;  // (j < i < n: already coloured, and owned)
     }
     int col = 0;
@@ -1014,13 +1021,22 @@ int build_colors(c8_ctx* c) {
     color[i] = col;
     nc = std::max(nc, col + 1);
   }
+  color_ptr->assign(nc + 1, 0);
+  for (int i = 0; i < n; ++i) (*color_ptr)[color[i] + 1]++;
+  for (int k = 0; k < nc; ++k) (*color_ptr)[k + 1] += (*color_ptr)[k];
+  color_nodes->assign(std::max(n, 0), 0);
+  std::vector<int32_t> at(color_ptr->begin(), color_ptr->end() - 1);
+  for (int i = 0; i < n; ++i) (*color_nodes)[at[color[i]]++] = i;
+}
+
+// the colour lists of the Gauss-Seidel sweeps from the host graph (greedy, ascending node id, smallest free colour) and
+// their device mirror: all nodes, or the owned nodes over the owned sub-graph when a halo is attached
+int build_colors(c8_ctx* c) {
+  int const want = c->halo ? c8_halo_num_owned(c->halo) : -1;
+  if (c->kry_colors_for == want) return C8_OK;
+  int const n = c->halo ? want : c->mesh.nnodes;
   c->kry_colors_for = -2;
-  c->kry_color_ptr.assign(nc + 1, 0);
-  for (int i = 0; i < n; ++i) c->kry_color_ptr[color[i] + 1]++;
-  for (int k = 0; k < nc; ++k) c->kry_color_ptr[k + 1] += c->kry_color_ptr[k];
-  c->kry_color_nodes.assign(std::max(n, 0), 0);
-  std::vector<int32_t> at(c->kry_color_ptr.begin(), c->kry_color_ptr.end() - 1);
-  for (int i = 0; i < n; ++i) c->kry_color_nodes[at[color[i]]++] = i;
+  color_graph(n, c->graph.nodeptr, c->graph.nodeadj, &c->kry_color_ptr, &c->kry_color_nodes);
   if (c->d_kry_colors) C8_HIP(hipFree(c->d_kry_colors));
   c->d_kry_colors = nullptr;
   if (n > 0) {
@@ -1038,7 +1054,8 @@ int build_colors(c8_ctx* c) {
 template <int ND, int NRES, int G>
 int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level;
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Solve q{};
   q.c = c;
   q.nn = c->mesh.nnodes;
@@ -1046,6 +1063,10 @@ int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], doub
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_precondition: empty mesh");
   if (two_level) {
     int const rcc = coarse_refusals(c, "c8_krylov_precondition");
+    if (rcc != C8_OK) return rcc;
+  }
+  if (multilevel) {
+    int const rcc = multilevel_refusals(c, "c8_krylov_precondition");
     if (rcc != C8_OK) return rcc;
   }
   if (nown <= 0) return C8_OK;
@@ -1084,11 +1105,13 @@ int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], doub
                             " is singular or not finite (node-block Jacobi preconditioner)");
   if (!std::isfinite(h.rr)) return fail(C8_ERR_ARG, "c8_krylov_precondition: the vector or the matrix is not finite");
   if (two_level && (rc = coarse_setup<ND, NRES, G>(q, true)) != C8_OK) return rc;
+  if (multilevel && (rc = multilevel_setup<ND, NRES, G>(q, -1)) != C8_OK) return rc;
   if (sgs) {
     hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
     if (two_level) C8_HIP((launch_coarse<ND, NRES>(q, q.s, q.shat)));
-    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, !two_level)));
+    if (multilevel) C8_HIP((launch_multilevel<ND, NRES>(q, q.s, q.shat)));
+    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, !two_level && !multilevel)));
   } else {
     hipLaunchKernelGGL((k_prec_own<ND, NRES, 1>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nn, q.nb_node, q.minv, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
@@ -1125,7 +1148,8 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level;
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Launchers L;
   if (c->ndims == 3 && two) L = launchers<3, 2, 16>(c->kry_precond);
   else if (c->ndims == 2 && two) L = launchers<2, 2, 8>(c->kry_precond);
@@ -1147,6 +1171,10 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve: empty mesh");
   int rc;
   if (two_level && (rc = coarse_refusals(c, "c8_krylov_solve")) != C8_OK) {
+    if (info) info->status = rc;
+    return rc;
+  }
+  if (multilevel && (rc = multilevel_refusals(c, "c8_krylov_solve")) != C8_OK) {
     if (info) info->status = rc;
     return rc;
   }
@@ -1190,6 +1218,7 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const tol = std::max(rel_tol * b_norm, abs_tol);
   q.tol2 = tol * tol;
   if (two_level && (rc = L.coarse(q, true)) != C8_OK) return rc;  // A_c = P^T A P and its inverse for this matrix
+  if (multilevel && (rc = L.levels(q, -1)) != C8_OK) return rc;   // every A_l and the inverse of the last one
 
   int restarts = 0, status = C8_NOT_CONVERGED;
   double true_norm = b_norm;
@@ -1248,6 +1277,7 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
   if (c->kry_precond == C8_PRECOND_TWO_LEVEL) return coarse_refusals(c, "c8_krylov_solve_parts");  // (a halo is attached: refused)
+  if (c->kry_precond == C8_PRECOND_MULTILEVEL) return multilevel_refusals(c, "c8_krylov_solve_parts");
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
   PartsLaunchers L;
   if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(sgs);
@@ -1377,7 +1407,7 @@ int c8_krylov_part_lists(c8_ctx* c, int32_t* num_interior, int32_t* num_boundary
 int c8_krylov_set_preconditioner(c8_ctx* c, int kind, int sweeps) {
   if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: null context");
   if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: a staged assembly is waiting for c8_gather_finish");
-  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL)
+  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL && kind != C8_PRECOND_MULTILEVEL)
     return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: unknown preconditioner " + std::to_string(kind));
   c->kry_precond = kind;
   c->kry_sweeps = sweeps > 0 ? sweeps : 1;
@@ -1435,6 +1465,99 @@ int c8_krylov_coarse_matrix(c8_ctx* c, const c8_system* sys, int32_t* n_coarse, 
   return C8_OK;
 }
 
+int c8_krylov_set_multilevel(c8_ctx* c, int32_t coarse_max, int32_t max_levels) {
+  if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_multilevel: null context");
+  if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_multilevel: a staged assembly is waiting for c8_gather_finish");
+  if (max_levels == 1) return fail(C8_ERR_ARG, "c8_krylov_set_multilevel: max_levels counts level 0 and must be at least 2");
+  c->kry_ml_coarse_max = coarse_max > 0 ? coarse_max : 0;
+  c->kry_ml_max_levels = max_levels > 0 ? max_levels : 0;
+  c->kry_ml_built = false;  // the levels are rebuilt at the next use
+  return C8_OK;
+}
+
+int c8_krylov_levels(c8_ctx* c, int32_t* num_levels) {
+  if (!c || !num_levels) return fail(C8_ERR_ARG, "c8_krylov_levels: null argument");
+  if (c->halo) return multilevel_refusals(c, "c8_krylov_levels");
+  if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_levels: empty mesh");
+  int const rc = build_levels(c);  // (reported with a last level above the cap too)
+  if (rc != C8_OK) return rc;
+  *num_levels = (int32_t)c->kry_levels.size() + 1;
+  return C8_OK;
+}
+
+int c8_krylov_level(c8_ctx* c, int32_t level, int32_t* num_nodes, const int32_t** aggregate_of_node, int32_t* num_colors,
+                    const int32_t** color_ptr, const int32_t** nodes) {
+  if (!c || !num_nodes || !aggregate_of_node || !num_colors || !color_ptr || !nodes) return fail(C8_ERR_ARG, "c8_krylov_level: null argument");
+  if (c->halo) return multilevel_refusals(c, "c8_krylov_level");
+  if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_level: empty mesh");
+  int rc = build_levels(c);
+  if (rc != C8_OK) return rc;
+  int const nl = (int)c->kry_levels.size();
+  if (level < 0 || level > nl) return fail(C8_ERR_ARG, "c8_krylov_level: level " + std::to_string(level) + " of " + std::to_string(nl + 1));
+  if (level == 0) {
+    if ((rc = build_colors(c)) != C8_OK) return rc;
+    *num_nodes = c->mesh.nnodes;
+    *aggregate_of_node = c->kry_agg_of.data();
+    *num_colors = (int32_t)c->kry_color_ptr.size() - 1;
+    *color_ptr = c->kry_color_ptr.data();
+    *nodes = c->kry_color_nodes.data();
+    return C8_OK;
+  }
+  c8_kry_level const& L = c->kry_levels[level - 1];
+  bool const last = level == nl;  // dense: no aggregates and no sweeps
+  *num_nodes = L.n;
+  *aggregate_of_node = last ? nullptr : L.agg_of.data();
+  *num_colors = last ? 0 : (int32_t)L.color_ptr.size() - 1;
+  *color_ptr = last ? nullptr : L.color_ptr.data();
+  *nodes = last ? nullptr : L.color_nodes.data();
+  return C8_OK;
+}
+
+int c8_krylov_level_matrix(c8_ctx* c, const c8_system* sys, int32_t level, int32_t* n_level, double* out_host) {
+  if (!c || !sys || !n_level) return fail(C8_ERR_ARG, "c8_krylov_level_matrix: null argument");
+  bool const two = c->nres == 2;
+  if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
+    return fail(C8_ERR_ARG, "c8_krylov_level_matrix: null array in the system");
+  int rc = multilevel_refusals(c, "c8_krylov_level_matrix");
+  if (rc != C8_OK) return rc;
+  int const nl = (int)c->kry_levels.size(), nc = coarse_columns(c);
+  if (level < 1 || level > nl)
+    return fail(C8_ERR_ARG, "c8_krylov_level_matrix: level " + std::to_string(level) + " is not one of the levels 1 .. " + std::to_string(nl));
+  c8_kry_level const& L = c->kry_levels[level - 1];
+  long long const nlong = (long long)L.n * nc;
+  if (nlong > COARSE_CAP)
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_level_matrix: level " + std::to_string(level) + " has " + std::to_string(nlong) +
+                                    " unknowns: a dense copy is refused above the cap of " + std::to_string(COARSE_CAP));
+  int const n = (int)nlong;
+  *n_level = n;
+  if (!out_host) return C8_OK;
+  Solve q{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  if (c->ndims == 3 && two) rc = multilevel_setup<3, 2, 16>(q, level);
+  else if (c->ndims == 2 && two) rc = multilevel_setup<2, 2, 8>(q, level);
+  else if (c->ndims == 2 && !two) rc = multilevel_setup<2, 1, 8>(q, level);
+  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_level_matrix: no kernels for this number of dimensions and residuals");
+  if (rc != C8_OK) return rc;
+  if (level == nl) {
+    int const lda = (n + 1) & ~1;
+    C8_HIP(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
+                            hipMemcpyDeviceToHost, c->stream));
+    C8_HIP(hipStreamSynchronize(c->stream));
+    return C8_OK;
+  }
+  std::vector<double> blocks(L.ga.size() * nc * nc);  // the block-sparse level, spread over the dense copy on the host
+  C8_HIP(hipMemcpyAsync(blocks.data(), L.d_A, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  C8_HIP(hipStreamSynchronize(c->stream));
+  std::fill(out_host, out_host + (size_t)n * n, 0.);
+  for (int i = 0; i < L.n; ++i)
+    for (int32_t e = L.gp[i]; e < L.gp[i + 1]; ++e)
+      for (int r = 0; r < nc; ++r)
+        for (int k = 0; k < nc; ++k) out_host[(size_t)(i * nc + r) * n + (size_t)L.ga[e] * nc + k] = blocks[((size_t)e * nc + r) * nc + k];
+  return C8_OK;
+}
+
 int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   if (!c || !sys || !v || !y) return fail(C8_ERR_ARG, "c8_krylov_precondition: null argument");
   bool const two = c->nres == 2;
@@ -1449,6 +1572,7 @@ int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const 
 }  // extern "C"
 
 void c8_krylov_release(c8_ctx* c) {
+  free_levels(c);
   if (c->kry_rocblas) (void)rocblas_destroy_handle((rocblas_handle)c->kry_rocblas);
   c->kry_rocblas = nullptr;
 }

@@ -10,7 +10,8 @@
 //                coarse_invert (in place) -> k_coarse_check; every solve, because the matrix changes every Newton iteration
 //   apply        k_restrict (r_c = P^T v) -> k_coarse_apply (e = A_c^-1 r_c) -> k_prolong (x = P e), then the sweeps of
 //                k_sgs_color started from this x
-// Every sum has a fixed order and no kernel uses a floating-point atomic.
+// Every sum has a fixed order and no kernel uses a floating-point atomic.  The multilevel kind (c8_krylov_multilevel.hpp) uses
+// the same aggregation (aggregate_graph) on every level, these kernels between levels 0 and 1, and the dense solve on its last level.
 constexpr int COARSE_CAP = 8192;          // n_coarse of the dense coarse solve: a 512 MB inverse
 constexpr size_t GALERKIN_LDS = 64 * 1024;  // largest tile of k_galerkin
 
@@ -87,8 +88,10 @@ struct AggTables {  // device mirror of the aggregates (c8_ctx::d_kry_agg and it
 // row in column order, and for the entries whose column node lies in the aggregate of `slot` adds P_i^T (A_ij P_j[:, c])
 // to its NC tile entries -- one owner per entry, the sum of an entry in one fixed order.  A column of P that is zero (every
 // row of the mode constrained, or a one-node aggregate's rotation) gets a unit diagonal.  The tile is then written to
-// A_c, every entry once; the other entries of A_c are the zeros of the memset before the launch.
-template <int ND, int NRES>
+// A_c, every entry once; the other entries of A_c are the zeros of the memset before the launch.  SPARSE (the multilevel
+// kind, c8_krylov_multilevel.hpp): the tile goes to the block-sparse A_1 instead, the NC x NC block of neighbour `slot` to
+// graph entry nbr_ptr[I] + slot of level 1; the sums are the same.
+template <int ND, int NRES, bool SPARSE = false>
 __global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj, Blocks A,
                                                   double* __restrict__ Ac, int lda) {
   constexpr int NB = CoarseDims<ND, NRES>::NB, NC = CoarseDims<ND, NRES>::NC;
@@ -157,7 +160,8 @@ __global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __
   __syncthreads();
   for (int idx = threadIdx.x; idx < NC * W; idx += TPB) {
     int const r = idx / W, q = idx % W;
-    Ac[(size_t)(I * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
+    if (SPARSE) Ac[((size_t)(b0 + q / NC) * NC + r) * NC + q % NC] = tile[idx];
+    else Ac[(size_t)(I * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
   }
 }
 
@@ -256,15 +260,20 @@ __global__ void __launch_bounds__(TPB) k_coarse_check(int n, int lda, double con
 
 inline int coarse_columns(c8_ctx const* c) { return c->ndims + (c->ndims == 3 ? 3 : 1) + (c->nres == 2 ? 1 : 0); }
 
-// The aggregates from the host node graph, once per context, and their device mirror.
+// The aggregates of a graph of n nodes (rows sorted, a node among its own neighbours) with positions x[n][3]:
 //   pass 1  nodes in ascending id: a node whose whole graph row (itself included) is free opens an aggregate of that row
 //   pass 2  nodes in ascending id: a free node joins the pass-1 aggregate of its lowest-id neighbour that pass 1 aggregated
 //   pass 3  nodes in ascending id: a node still free becomes an aggregate of its own
-int build_aggregates(c8_ctx* c) {
-  if (c->kry_nagg >= 0) return C8_OK;
-  int const nn = c->mesh.nnodes, nd = c->ndims;
-  std::vector<int32_t> const &gp = c->graph.nodeptr, &ga = c->graph.nodeadj;
-  std::vector<int32_t> agg(nn, -1);
+struct Aggregates {
+  int nagg = 0, max_nbr = 0;                          // max_nbr: most neighbouring aggregates of one aggregate (itself included)
+  std::vector<int32_t> agg, ptr, nodes, nbr_ptr, nbr, slot;
+  std::vector<double> off;                            // [n][nd] node - centroid of its aggregate
+  std::vector<double> centroid;                       // [nagg][3]
+};
+Aggregates aggregate_graph(int nn, int nd, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, double const* x) {
+  Aggregates H;
+  std::vector<int32_t>& agg = H.agg;
+  agg.assign(nn, -1);
   int nagg = 0;
   for (int i = 0; i < nn; ++i) {
     bool free_row = true;
@@ -282,24 +291,28 @@ int build_aggregates(c8_ctx* c) {
   for (int i = 0; i < nn; ++i)
     if (agg[i] < 0) agg[i] = nagg++;
   // node lists (ascending id), centroids, offsets
-  std::vector<int32_t> ptr(nagg + 1, 0), nodes(nn);
+  std::vector<int32_t>&ptr = H.ptr, &nodes = H.nodes;
+  ptr.assign(nagg + 1, 0), nodes.assign(nn, 0);
   for (int i = 0; i < nn; ++i) ptr[agg[i] + 1]++;
   for (int a = 0; a < nagg; ++a) ptr[a + 1] += ptr[a];
   {
     std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);
     for (int i = 0; i < nn; ++i) nodes[at[agg[i]]++] = i;
   }
-  std::vector<double> off((size_t)nn * nd);
+  H.off.assign((size_t)nn * nd, 0.);
+  H.centroid.assign((size_t)nagg * 3, 0.);
   for (int a = 0; a < nagg; ++a)
     for (int d = 0; d < nd; ++d) {
       double sum = 0.;
-      for (int k = ptr[a]; k < ptr[a + 1]; ++k) sum += c->mesh.coords[(size_t)nodes[k] * 3 + d];
+      for (int k = ptr[a]; k < ptr[a + 1]; ++k) sum += x[(size_t)nodes[k] * 3 + d];
       double const mean = sum / (double)(ptr[a + 1] - ptr[a]);
-      for (int k = ptr[a]; k < ptr[a + 1]; ++k) off[(size_t)nodes[k] * nd + d] = c->mesh.coords[(size_t)nodes[k] * 3 + d] - mean;
+      H.centroid[(size_t)a * 3 + d] = mean;
+      for (int k = ptr[a]; k < ptr[a + 1]; ++k) H.off[(size_t)nodes[k] * nd + d] = x[(size_t)nodes[k] * 3 + d] - mean;
     }
   // neighbouring aggregates of every aggregate (ascending id, itself included) and the slot of every graph entry
-  std::vector<int32_t> nbr_ptr(nagg + 1, 0), nbr, slot(ga.size()), where(nagg, -1);
-  int max_nbr = 0;
+  std::vector<int32_t>&nbr_ptr = H.nbr_ptr, &nbr = H.nbr, &slot = H.slot;
+  std::vector<int32_t> where(nagg, -1);
+  nbr_ptr.assign(nagg + 1, 0), slot.assign(ga.size(), 0);
   for (int a = 0; a < nagg; ++a) {
     size_t const lo = nbr.size();
     for (int k = ptr[a]; k < ptr[a + 1]; ++k)
@@ -307,32 +320,49 @@ int build_aggregates(c8_ctx* c) {
         if (where[agg[ga[e]]] != a) { where[agg[ga[e]]] = a; nbr.push_back(agg[ga[e]]); }
     std::sort(nbr.begin() + lo, nbr.end());
     nbr_ptr[a + 1] = (int32_t)nbr.size();
-    max_nbr = std::max(max_nbr, (int)(nbr.size() - lo));
+    H.max_nbr = std::max(H.max_nbr, (int)(nbr.size() - lo));
     for (int k = ptr[a]; k < ptr[a + 1]; ++k)
       for (int32_t e = gp[nodes[k]]; e < gp[nodes[k] + 1]; ++e)
         slot[e] = (int32_t)(std::lower_bound(nbr.begin() + lo, nbr.end(), agg[ga[e]]) - (nbr.begin() + lo));
   }
-  // one device buffer of int32: agg_of, ptr, nodes, nbr_ptr, nbr, slot
+  H.nagg = nagg;
+  return H;
+}
+
+// the device mirror of the aggregates: one buffer of int32 (agg_of, ptr, nodes, nbr_ptr, nbr, slot; at[k] = where each
+// starts) and the offsets
+int upload_aggregates(Aggregates const& H, int32_t** d_agg, size_t at[6], double** d_off) {
   std::vector<int32_t> pack;
-  size_t o[6];
-  std::vector<int32_t> const* parts[6] = {&agg, &ptr, &nodes, &nbr_ptr, &nbr, &slot};
+  std::vector<int32_t> const* parts[6] = {&H.agg, &H.ptr, &H.nodes, &H.nbr_ptr, &H.nbr, &H.slot};
   for (int k = 0; k < 6; ++k) {
-    o[k] = pack.size();
+    at[k] = pack.size();
     pack.insert(pack.end(), parts[k]->begin(), parts[k]->end());
   }
+  *d_agg = nullptr, *d_off = nullptr;
+  C8_HIP(hipMalloc((void**)d_agg, pack.size() * sizeof(int32_t)));
+  C8_HIP(hipMemcpy(*d_agg, pack.data(), pack.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  C8_HIP(hipMalloc((void**)d_off, H.off.size() * sizeof(double)));
+  C8_HIP(hipMemcpy(*d_off, H.off.data(), H.off.size() * sizeof(double), hipMemcpyHostToDevice));
+  return C8_OK;
+}
+
+// The aggregates of the context's node graph, once per context, and their device mirror; the graph and the positions of
+// level 1 (the neighbour lists and the centroids) stay on the host for the multilevel kind.
+int build_aggregates(c8_ctx* c) {
+  if (c->kry_nagg >= 0) return C8_OK;
+  int const nn = c->mesh.nnodes;
+  Aggregates H = aggregate_graph(nn, c->ndims, c->graph.nodeptr, c->graph.nodeadj, c->mesh.coords.data());
   if (c->d_kry_agg) C8_HIP(hipFree(c->d_kry_agg));
   if (c->d_kry_agg_off) C8_HIP(hipFree(c->d_kry_agg_off));
   if (c->d_kry_cflags) C8_HIP(hipFree(c->d_kry_cflags));
   c->d_kry_agg = nullptr, c->d_kry_agg_off = nullptr, c->d_kry_cflags = nullptr;
-  C8_HIP(hipMalloc((void**)&c->d_kry_agg, pack.size() * sizeof(int32_t)));
-  C8_HIP(hipMemcpy(c->d_kry_agg, pack.data(), pack.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  C8_HIP(hipMalloc((void**)&c->d_kry_agg_off, off.size() * sizeof(double)));
-  C8_HIP(hipMemcpy(c->d_kry_agg_off, off.data(), off.size() * sizeof(double), hipMemcpyHostToDevice));
+  int const rc = upload_aggregates(H, &c->d_kry_agg, c->kry_agg_at, &c->d_kry_agg_off);
+  if (rc != C8_OK) return rc;
   C8_HIP(hipMalloc((void**)&c->d_kry_cflags, (size_t)nn * sizeof(int32_t)));
-  for (int k = 0; k < 6; ++k) c->kry_agg_at[k] = o[k];
-  c->kry_agg_of = agg;
-  c->kry_agg_max_nbr = max_nbr;
-  c->kry_nagg = nagg;
+  c->kry_agg_of = std::move(H.agg);
+  c->kry_agg_nbr_ptr = std::move(H.nbr_ptr), c->kry_agg_nbr = std::move(H.nbr), c->kry_agg_x = std::move(H.centroid);
+  c->kry_agg_max_nbr = H.max_nbr;
+  c->kry_nagg = H.nagg;
   return C8_OK;
 }
 

@@ -11,6 +11,7 @@ C8_SCATTER_ATOMIC, C8_SCATTER_COLORED, C8_SCATTER_GATHER = 0, 1, 2
 C8_KERNEL_AUTO, C8_KERNEL_SLOT, C8_KERNEL_WAVE, C8_KERNEL_WAVE_AD, C8_KERNEL_NODE = 0, 1, 2, 3, 4
 C8_SCALE_NONE, C8_SCALE_LOG, C8_SCALE_BOUNDS = 0, 1, 2
 C8_PRECOND_BLOCK_JACOBI, C8_PRECOND_BLOCK_SGS, C8_PRECOND_TWO_LEVEL = 0, 1, 3  # (2 is not a kind: refused)
+C8_PRECOND_MULTILEVEL = 5  # (nor is 4)
 
 dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
@@ -187,6 +188,10 @@ SYMBOLS = [
     ("c8_krylov_colors", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p), C.POINTER(i32p)]),
     ("c8_krylov_aggregates", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p)]),
     ("c8_krylov_coarse_matrix", C.c_int, [C.c_void_p, C.POINTER(System), i32p, dp]),
+    ("c8_krylov_set_multilevel", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    ("c8_krylov_levels", C.c_int, [C.c_void_p, i32p]),
+    ("c8_krylov_level", C.c_int, [C.c_void_p, C.c_int32, i32p, C.POINTER(i32p), i32p, C.POINTER(i32p), C.POINTER(i32p)]),
+    ("c8_krylov_level_matrix", C.c_int, [C.c_void_p, C.POINTER(System), C.c_int32, i32p, dp]),
     ("c8_krylov_precondition", C.c_int, [C.c_void_p, C.POINTER(System), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("c8_transform_params", C.c_int, [C.c_int, dp, i32p, dp, dp, C.c_int, dp]),
     ("c8_transform_gradient", C.c_int, [C.c_int, dp, dp, i32p, dp, dp, dp]),

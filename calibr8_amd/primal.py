@@ -76,7 +76,8 @@ def device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditioner="jacobi", 
     """Linear solve on the device: right-preconditioned BiCGStab (c8_krylov_solve) with node-block Jacobi, or with
     preconditioner="sgs" `sweeps` symmetric multicolour node-block Gauss-Seidel sweeps, or with preconditioner="two_level" a
     coarse correction over node aggregates ahead of those sweeps (C8_PRECOND_TWO_LEVEL: dense coarse solve, refused above
-    8192 coarse unknowns).  The preconditioner is state of the
+    8192 coarse unknowns), or with preconditioner="multilevel" that construction repeated on the coarse matrix
+    (C8_PRECOND_MULTILEVEL: no such cap on the mesh; Assembler.set_krylov_multilevel).  The preconditioner is state of the
     assembler's context: this call SETS it (Assembler.set_krylov_preconditioner, refused while a staged assembly waits for
     gather_finish), the default "jacobi" included, so it overrides an earlier choice and holds for every solver on `asm`.
     Usable wherever `scipy_solver(asm)` is: PrimalDriver(solver=device_solver(asm)), hence adjoint_gradient, InverseProblem,
@@ -91,7 +92,8 @@ def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditione
     rank's owned rows stay on its device.  Usable wherever `distributed_scipy_solver(asm, plan, dist)` is: PrimalDriver,
     hence adjoint_gradient, InverseProblem and FEMUProblem over parts.  `asm` is the part's assembler, with its Halo attached
     before the first solve; every rank must make the same calls (the solve is collective).  preconditioner, sweeps and opts as
-    for `device_solver`; "sgs" is part-local here (columns owned by other parts are dropped inside the sweeps)."""
+    for `device_solver`; "sgs" is part-local here (columns owned by other parts are dropped inside the sweeps); "two_level" and
+    "multilevel" cover one part only and the library refuses them here."""
     return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, preconditioner=preconditioner, sweeps=sweeps, **opts)
 
 

@@ -376,7 +376,8 @@ int c8_adjoint_solve_step(c8_ctx* ctx, const c8_state* st, const c8_system* sys,
  * iterations at about three times the matrix traffic per iteration, the same growth with 1 / h, the same
  * reproducibility; or C8_PRECOND_TWO_LEVEL, which adds a coarse space of rigid-body modes per aggregate of nodes:
  * two levels, dense coarse solve, capped at 8192 coarse unknowns (meshes up to roughly 10^5 nodes).  It is no
- * multilevel method: a recursive coarse solve is what would lift that cap. */
+ * multilevel method; C8_PRECOND_MULTILEVEL is: it repeats the aggregation on the coarse matrix until that is small and
+ * inverts only the last level densely, which lifts the cap. */
 typedef struct {
   int32_t max_iters;      /* iterations (two A x each); default 20000 when <= 0 */
   int32_t check_every;    /* host reads the residual norm every this many iterations; default 10 */
@@ -458,8 +459,9 @@ int c8_krylov_part_lists(c8_ctx* ctx, int32_t* num_interior, int32_t* num_bounda
  *             column of P that is zero (every row of a mode constrained; the rotations of a one-node aggregate) gets a
  *             unit diagonal.  n_coarse = aggregates x columns must not exceed 8192 (a 512 MB inverse): above it the solve
  *             and the apply return C8_ERR_UNSUPPORTED, the message names n_coarse and the cap, nothing is iterated.  That
- *             makes this kind a method for meshes up to roughly 10^5 nodes; a recursive (multilevel) coarse solve is what
- *             lifts the cap.  A_c singular or not finite: C8_ERR_ARG, the message names the aggregate.
+ *             makes this kind a method for meshes up to roughly 10^5 nodes; the recursive coarse solve of
+ *             C8_PRECOND_MULTILEVEL below lifts the cap.  A_c singular or not finite: C8_ERR_ARG, the message names the
+ *             aggregate.
  *   y = M^-1 v   x = P A_c^-1 P^T v, then the symmetric sweeps above started from this x instead of 0 (every colour launch
  *             reads the whole graph row); y = x.  A fixed linear operator: BiCGStab stays valid.
  * Reproducibility: every kernel of this library in the set-up and in the apply sums in a fixed order without
@@ -470,7 +472,40 @@ int c8_krylov_part_lists(c8_ctx* ctx, int32_t* num_interior, int32_t* num_bounda
 enum { C8_PRECOND_BLOCK_JACOBI = 0, C8_PRECOND_BLOCK_SGS = 1 };
 enum { C8_PRECOND_TWO_LEVEL = 3 };  /* 2 stays unassigned: callers have been told since the Gauss-Seidel kind that
                                        2 is refused as an unknown kind, and it still is */
+/* C8_PRECOND_MULTILEVEL repeats the two-level construction on the coarse matrix: a V-cycle of `sweeps` symmetric sweeps per
+ * level (sweeps <= 0: one) over a dense solve on the last level.  One part only: with a halo attached every call that would
+ * use it (c8_krylov_solve_parts, c8_krylov_precondition, c8_krylov_levels, c8_krylov_level, c8_krylov_level_matrix) returns
+ * C8_ERR_UNSUPPORTED, one rank included; the message says "multilevel" and "halo".  NC = the columns per aggregate of the
+ * two-level kind (7, 4 or 3).
+ *   levels    Level 0 is the system: node blocks over the node graph.  Level l >= 1 has one node per aggregate of level
+ *             l - 1, with NC unknowns (the rigid-body modes, then p) and a position: the aggregate's centroid (the unweighted
+ *             mean of its members' positions, summed in ascending id).  Graph of level l + 1: I and J are neighbours when a
+ *             node of I is a neighbour of a node of J in the graph of level l, self included.  Aggregates and colours of
+ *             every level come from that level's graph by the two host rules above, unchanged.  Level 1 always exists;
+ *             another level is built while n_l x NC > coarse_max, fewer than max_levels levels exist (level 0 counts) and
+ *             aggregation still reduces the node count.
+ *   P_l       P_0 is the P of the two-level kind.  l >= 1, node a of level l in aggregate I: d = x_a - centroid(I); the
+ *             NC x NC block is the identity (translations, rotations, p pass to themselves) plus rotation m -> translation
+ *             e_m x d (2-D: (-d_y, d_x)).  At every level a row of P_l is zero when its equation in A_l is constrained by
+ *             the rule above (every off-diagonal entry of the row exactly 0): the Dirichlet rows on level 0, the
+ *             unit-diagonal unknowns of zero columns on the coarser levels.
+ *   A_l+1     = P_l^T A_l P_l, a zero column of P_l gets a unit diagonal; block-sparse over the level's graph except the
+ *             last level, which is dense and inverted as A_c above.  The last level must not exceed the 8192 of the
+ *             two-level kind: otherwise C8_ERR_UNSUPPORTED, the message names its size, the cap and what ended the recursion
+ *             (max_levels, or aggregation that no longer reduces), nothing is iterated.
+ *   M_l^-1 v  on the last level the dense inverse times v; otherwise x = P_l M_l+1^-1 P_l^T v, then `sweeps` symmetric
+ *             multicolour block Gauss-Seidel sweeps on A_l started from x, with that level's colours and the inverses of its
+ *             NC x NC (level 0: node) diagonal blocks, every colour launch over the whole row.  M^-1 = M_0^-1: a fixed
+ *             linear operator.  With max_levels = 2, or when level 1 fits coarse_max, it is the two-level operator.
+ * A singular or non-finite diagonal block: C8_ERR_ARG; on level 0 the message names the node, on a coarser level the level
+ * and the aggregate.  Every sum of the set-up and of the apply has a fixed order (no floating-point atomics); the inverse of
+ * the last level comes from rocSOLVER as above. */
+enum { C8_PRECOND_MULTILEVEL = 5 };
 int c8_krylov_set_preconditioner(c8_ctx* ctx, int kind, int sweeps);
+/* The two settings of C8_PRECOND_MULTILEVEL (<= 0: the default): coarse_max, default 1024 unknowns, and max_levels, default
+ * 8, at least 2.  The levels are rebuilt at the next use.  C8_ERR_ARG for a null context, for max_levels = 1, and while a
+ * staged assembly waits for c8_gather_finish. */
+int c8_krylov_set_multilevel(c8_ctx* ctx, int32_t coarse_max, int32_t max_levels);
 int c8_krylov_get_preconditioner(const c8_ctx* ctx);  /* C8_PRECOND_* (C8_ERR_ARG for a null context) */
 /* Diagnostic / test access: the colour lists of the Gauss-Seidel sweeps (HOST arrays owned by the context, built at the
  * first use, rebuilt when a halo has been attached since): nodes[color_ptr[c] .. color_ptr[c + 1]) are the nodes of
@@ -484,6 +519,19 @@ int c8_krylov_aggregates(c8_ctx* ctx, int32_t* num_aggregates, const int32_t** a
  * selected) and copies the dense row-major n_coarse x n_coarse matrix to out_host (HOST memory); out_host NULL returns
  * n_coarse only.  C8_ERR_UNSUPPORTED with a halo attached or above the cap. */
 int c8_krylov_coarse_matrix(c8_ctx* ctx, const c8_system* sys, int32_t* n_coarse, double* out_host);
+/* Diagnostic / test access: the levels of C8_PRECOND_MULTILEVEL under the current settings (HOST arrays owned by the
+ * context, built at the first use, valid until c8_krylov_set_multilevel or c8_destroy).  c8_krylov_levels: their number,
+ * level 0 included; reported with a last level above the cap too.  c8_krylov_level, level in [0, num_levels): the node
+ * count, the aggregate of every node and the colour lists in the layout of c8_krylov_colors; the last level has neither
+ * (aggregate_of_node, color_ptr, nodes = NULL, num_colors = 0).  C8_ERR_UNSUPPORTED with a halo attached. */
+int c8_krylov_levels(c8_ctx* ctx, int32_t* num_levels);
+int c8_krylov_level(c8_ctx* ctx, int32_t level, int32_t* num_nodes, const int32_t** aggregate_of_node, int32_t* num_colors,
+                    const int32_t** color_ptr, const int32_t** nodes);
+/* Diagnostic / test access: runs the set-up of C8_PRECOND_MULTILEVEL on `sys` up to A_level, level in [1, num_levels)
+ * (whatever kind is selected), and copies it as a dense row-major n_level x n_level matrix to out_host (HOST memory);
+ * out_host NULL returns n_level only.  C8_ERR_UNSUPPORTED with a halo attached, and when this level or the last one is
+ * above the cap. */
+int c8_krylov_level_matrix(c8_ctx* ctx, const c8_system* sys, int32_t level, int32_t* n_level, double* out_host);
 /* y = M^-1 v, once, with the context's current preconditioner: the block inverses and the kernels of the solve, and its
  * refusals (C8_ERR_ARG for a singular diagonal block, the node named, and for a vector or matrix that is not finite).
  * v and y are DEVICE pointers laid out as b and dx (v[1], y[1] unused when c8_num_residuals() == 1).  Not collective: with

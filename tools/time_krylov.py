@@ -5,11 +5,12 @@ The events are recorded on torch's current stream, which is the stream the Assem
 solve synchronises that stream at every host read and before it returns, so the time between the two events is the whole
 solve as the caller sees it: kernels, launch gaps and the host reads every check_every iterations.
 --lib F times another build of libc8.so (an earlier commit's, say): entry points it lacks are left unbound and the
-preconditioners it cannot select are skipped.  --profile runs one solve per mesh with the kind of --profile-kind (sgs, or
-two_level) and nothing else (for rocprofv3 --kernel-trace --stats -- python tools/time_krylov.py --profile).
+preconditioners it cannot select are skipped.  --profile runs one solve per mesh with the kind of --profile-kind (sgs,
+two_level or multilevel) and nothing else (for rocprofv3 --kernel-trace --stats -- python tools/time_krylov.py --profile).
 For the two-level kind the set-up of the coarse level (constrained-row flags, A_c = P^T A P, its dense inverse) is timed on
 its own as the time of one c8_krylov_precondition call minus the time of the same call with the Gauss-Seidel kind: the
-two calls differ by that set-up and one coarse correction; n_coarse is printed beside it."""
+two calls differ by that set-up and one coarse correction; n_coarse is printed beside it.  The multilevel kind is timed once
+per value of --coarse-max (0: the library's default), its set-up in the same way, with the nodes of every level printed."""
 import argparse
 import ctypes as C
 import os
@@ -47,7 +48,8 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--meshes", default="notched_bar(48,12,12);brick(40,40,40)")
     ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--profile-kind", default="sgs", choices=["sgs", "two_level"])
+    ap.add_argument("--profile-kind", default="sgs", choices=["sgs", "two_level", "multilevel"])
+    ap.add_argument("--coarse-max", default="0", help="comma-separated coarse_max values of the multilevel kind (0: the default)")
     a = ap.parse_args()
     import torch  # before any libc8.so is loaded: the library has to bind to torch's HIP runtime (calibr8_amd/lib.py)
     from calibr8_amd import lib
@@ -58,9 +60,12 @@ def main():
     L = lib.load_library()
     has_sgs = hasattr(L, "c8_krylov_set_preconditioner") and any(s[0] == "c8_krylov_set_preconditioner" for s in lib.SYMBOLS)
     has_two = has_sgs and any(s[0] == "c8_krylov_aggregates" for s in lib.SYMBOLS)
+    has_multi = has_two and any(s[0] == "c8_krylov_set_multilevel" for s in lib.SYMBOLS)
     kinds = [("jacobi", 0)] + ([("sgs", 1)] if has_sgs else []) + ([("two_level", lib.C8_PRECOND_TWO_LEVEL)] if has_two else [])
+    if has_multi:
+        kinds += [("multilevel:%d" % int(v), lib.C8_PRECOND_MULTILEVEL) for v in a.coarse_max.split(",")]
     if a.profile:
-        kinds, a.reps = [k for k in kinds if k[0] == a.profile_kind], 1
+        kinds, a.reps = [k for k in kinds if k[0].split(":")[0] == a.profile_kind], 1
     for name in a.meshes.split(";"):
         asm, ls = build_system(name)
         n = asm.nnodes * (asm.ndims + 1)
@@ -77,6 +82,15 @@ def main():
                 if na.value * 7 > 8192:
                     print("%-10s %-22s unknowns %7d two_level skipped: n_coarse %d exceeds the cap of the dense coarse solve" % (a.tag, name, n, na.value * 7), flush=True)
                     continue
+            levels = []
+            if code == getattr(lib, "C8_PRECOND_MULTILEVEL", -1):
+                lib.check(L.c8_krylov_set_multilevel(asm.h, int(kind.split(":")[1]), 0))
+                nl, nn_, nc_ = C.c_int32(), C.c_int32(), C.c_int32()
+                p1, p2, p3 = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+                lib.check(L.c8_krylov_levels(asm.h, C.byref(nl)))
+                for lev in range(nl.value):
+                    lib.check(L.c8_krylov_level(asm.h, lev, C.byref(nn_), C.byref(p1), C.byref(nc_), C.byref(p2), C.byref(p3)))
+                    levels.append((nn_.value, nc_.value))
 
             def solve():
                 lib.check(L.c8_krylov_solve(asm.h, C.byref(sy), ptrs, None, C.byref(info)))
@@ -92,7 +106,7 @@ def main():
                 torch.cuda.synchronize()
                 t.append(s.elapsed_time(e))
             ms = float(np.median(t))
-            if kind == "two_level" and not a.profile:
+            if (kind == "two_level" or levels) and not a.profile:
                 def apply_ms(code_):
                     lib.check(L.c8_krylov_set_preconditioner(asm.h, code_, 1))
                     tt = []
@@ -105,10 +119,14 @@ def main():
                         torch.cuda.synchronize()
                         tt.append(s.elapsed_time(e))
                     return float(np.median(tt[1:]))
-                t_sgs, t_two = apply_ms(lib.C8_PRECOND_BLOCK_SGS), apply_ms(lib.C8_PRECOND_TWO_LEVEL)
-                print("%-10s %-22s two_level: aggregates %d n_coarse %d, set-up of the coarse level %.2f ms (one apply with set-up %.2f ms, "
-                      "the same with sgs %.2f ms)" % (a.tag, name, na.value, na.value * 7, t_two - t_sgs, t_two, t_sgs), flush=True)
-            print("%-10s %-22s unknowns %7d %-7s iterations %5d restarts %d  %9.2f ms per solve  %7.1f us per iteration  (min %.2f max %.2f ms, residual %.2e)" %
+                t_sgs, t_two = apply_ms(lib.C8_PRECOND_BLOCK_SGS), apply_ms(code)
+                if levels:
+                    print("%-10s %-22s %s: nodes per level %s colours per level %s, set-up of the levels %.2f ms (one apply with set-up %.2f ms, "
+                          "the same with sgs %.2f ms)" % (a.tag, name, kind, [v[0] for v in levels], [v[1] for v in levels], t_two - t_sgs, t_two, t_sgs), flush=True)
+                else:
+                    print("%-10s %-22s two_level: aggregates %d n_coarse %d, set-up of the coarse level %.2f ms (one apply with set-up %.2f ms, "
+                          "the same with sgs %.2f ms)" % (a.tag, name, na.value, na.value * 7, t_two - t_sgs, t_two, t_sgs), flush=True)
+            print("%-10s %-22s unknowns %7d %-15s iterations %5d restarts %d  %9.2f ms per solve  %7.1f us per iteration  (min %.2f max %.2f ms, residual %.2e)" %
                   (a.tag, name, n, kind, info.iters, info.restarts, ms, 1e3 * ms / max(info.iters, 1), min(t), max(t),
                    info.residual_norm / info.b_norm), flush=True)
 
