@@ -199,7 +199,7 @@ void c8_destroy(c8_ctx* c) {
   for (hipEvent_t e : c->ev_asm) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_sum) (void)hipEventDestroy(e);
   if (c->sum_stream) (void)hipStreamDestroy(c->sum_stream);
-  void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv};
+  void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
   for (void* b : bufs) (void)hipFree(b);
   c8_krylov_release(c);
   delete c;

@@ -153,6 +153,18 @@ struct c8_ctx {
   int kry_ml_coarse_max = 0, kry_ml_max_levels = 0;   // (set by c8_krylov.hip: <= 0 until the first use = the defaults)
   bool kry_ml_built = false;
   std::vector<c8_kry_level> kry_levels;               // [k] is level k + 1; freed by c8_krylov_release
+  // ... the coarse level of C8_PRECOND_TWO_LEVEL_PARTS (c8_krylov_parts_coarse.hpp): aggregates of the owned sub-graph
+  int kry_pc_host_for = -1;          // num_owned the host lists and the counts were built for (-1: not built)
+  int kry_pc_for = -1;               // num_owned the device tables were built for (-1: not built; reset by c8_halo_attach)
+  int kry_pc_nagg = 0, kry_pc_max_nbr = 0, kry_pc_bad = -1;  // this rank's aggregates; widest block row; bad row of the last set-up
+  long long kry_pc_base = 0, kry_pc_total = 0;               // aggregates of the ranks below this one, of all ranks
+  std::vector<int32_t> kry_pc_agg_of, kry_pc_ptr, kry_pc_nodes;  // [num_owned] LOCAL aggregate ids; node lists of the aggregates
+  std::vector<double> kry_pc_off;    // [num_owned][ndims] node - centroid
+  int32_t* d_kry_pc_agg = nullptr;   // layout of d_kry_agg: GLOBAL aggregate of every local node, node lists, neighbour lists, slots
+  size_t kry_pc_at[6] = {0, 0, 0, 0, 0, 0};
+  double* d_kry_pc_off = nullptr;    // [nnodes][ndims], the copies' entries imported from their owners
+  int32_t* d_kry_pc_flags = nullptr; // [nnodes] constrained-row flags of the current matrix, the copies' imported
+  double* d_kry_pc_imp = nullptr;    // a vector's worth of doubles: what the import tables move the ids and the flags in
 };
 void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
@@ -178,3 +190,5 @@ int c8_halo_import_start(c8_halo* h, double* v0, double* v1, bool degraded);   /
 int c8_halo_import_finish(c8_halo* h, double* v0, double* v1, bool degraded);  // ... store what arrived in the copies
 // in-place SUM over the ranks of n <= 64 doubles in DEVICE memory, ordered after and before the work on `stream`
 int c8_comm_allreduce_device(c8_comm* cm, hipStream_t stream, double* d_values, int n, bool degraded);
+// ... of a device buffer of any length (the coarse matrix and the coarse residual of C8_PRECOND_TWO_LEVEL_PARTS)
+int c8_comm_allreduce_device_long(c8_comm* cm, hipStream_t stream, double* d_values, size_t n, bool degraded);

@@ -21,6 +21,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -145,6 +146,8 @@ struct c8_comm {
   hipStream_t stream = nullptr;          // RCCL transport: the stream the messages travel on
   double* d_small = nullptr;             // device scratch of the small all-reduce
   double* h_small = nullptr;             // host transport: pinned staging of the device-buffer all-reduce (at its first use)
+  double* h_long = nullptr;              // ... of c8_comm_allreduce_device_long, grown to the longest buffer seen
+  size_t h_long_n = 0;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // RCCL transport: order the device-buffer all-reduce against the caller's stream
   c8_host_exchange_fn host_exchange = nullptr;
   c8_host_allreduce_fn host_allreduce = nullptr;
@@ -333,6 +336,43 @@ int c8_comm_allreduce_device(c8_comm* cm, hipStream_t stream, double* d_values, 
   C8H_HIP(hipMemcpyAsync(d_values, cm->h_small, n * sizeof(double), hipMemcpyHostToDevice, stream));
   return C8_OK;
 }
+// The same for a device buffer of any length.  RCCL: one ncclAllReduce in place between the two events.  Host transport: a
+// pinned host buffer of the needed size, then the callback (a degraded rank enters it with NaN, as above).
+int c8_comm_allreduce_device_long(c8_comm* cm, hipStream_t stream, double* d_values, size_t n, bool degraded) {
+  if (!cm || (!d_values && !degraded) || n < 1 || n > (size_t)INT_MAX) return c8_fail(C8_ERR_ARG, "c8_comm_allreduce_device_long: bad argument");
+  if (cm->nccl) {
+    if (degraded) return C8_ERR_DEVICE;
+    C8H_HIP(hipEventRecord(cm->ev_in, stream));
+    C8H_HIP(hipStreamWaitEvent(cm->stream, cm->ev_in, 0));
+    C8H_NCCL(rccl().AllReduce(d_values, d_values, n, ncclDouble, ncclSum, cm->nccl, cm->stream));
+    C8H_HIP(hipEventRecord(cm->ev_out, cm->stream));
+    C8H_HIP(hipStreamWaitEvent(stream, cm->ev_out, 0));
+    return C8_OK;
+  }
+  if (cm->nranks == 1) return C8_OK;
+  hipError_t err = hipSuccess;
+  if (!degraded) {
+    if (cm->h_long_n < n) {
+      // (the last copy up from the old buffer may still be in flight on the stream it was enqueued on)
+      err = hipStreamSynchronize(stream);
+      if (cm->h_long) (void)hipHostFree(cm->h_long);
+      cm->h_long = nullptr;
+      cm->h_long_n = 0;
+      if (err == hipSuccess) err = hipHostMalloc((void**)&cm->h_long, n * sizeof(double), hipHostMallocDefault);
+      if (err == hipSuccess) cm->h_long_n = n;
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(cm->h_long, d_values, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+  }
+  if (degraded || err != hipSuccess) {  // the other ranks are waiting in the callback: enter it, with values that stop them
+    std::vector<double> nan(n, std::nan(""));
+    (void)cm->host_allreduce(cm->user, nan.data(), (int)n);
+    return degraded ? C8_ERR_DEVICE : c8_fail(C8_ERR_DEVICE, std::string("c8_comm_allreduce_device_long: ") + hipGetErrorString(err));
+  }
+  if (cm->host_allreduce(cm->user, cm->h_long, (int)n) != 0) return c8_fail(C8_ERR_ARG, "c8_comm_allreduce_device_long: the host all-reduce callback failed");
+  C8H_HIP(hipMemcpyAsync(d_values, cm->h_long, n * sizeof(double), hipMemcpyHostToDevice, stream));
+  return C8_OK;
+}
 void c8_halo_detach_ctx(c8_ctx* c) {
   c8_halo* h = c->halo;
   if (!h) return;
@@ -400,6 +440,7 @@ void c8_comm_destroy(c8_comm* cm) {
   if (cm->stream) (void)hipStreamDestroy(cm->stream);
   (void)hipFree(cm->d_small);
   if (cm->h_small) (void)hipHostFree(cm->h_small);
+  if (cm->h_long) (void)hipHostFree(cm->h_long);
   if (cm->ev_in) (void)hipEventDestroy(cm->ev_in);
   if (cm->ev_out) (void)hipEventDestroy(cm->ev_out);
   delete cm;
@@ -602,6 +643,7 @@ int c8_halo_attach(c8_halo* h, c8_ctx* c, c8_comm* cm) {
   h->comm = cm;
   c->halo = h;
   c->num_parts = cm->nranks;
+  c->kry_pc_host_for = -1, c->kry_pc_for = -1;  // the aggregates over parts and their imported data belong to one attached halo
   return C8_OK;
 }
 

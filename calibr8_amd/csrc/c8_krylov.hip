@@ -20,6 +20,8 @@
 // every other launch of the iteration is the same.  With C8_PRECOND_TWO_LEVEL the sweeps start from the coarse correction
 // x = P A_c^-1 P^T rhs instead of 0 (k_restrict, k_coarse_apply, k_prolong after k_vec; c8_krylov_coarse.hpp, DESIGN.md
 // section 13d), and the set-up of a solve forms A_c and its dense inverse.
+// C8_PRECOND_TWO_LEVEL_PARTS is that kind without a halo; over parts it is the coarse space of c8_krylov_parts_coarse.hpp
+// (DESIGN.md section 13f): part-local aggregates, a dense global A_c replicated on every rank, two more all-reduces per apply.
 // With C8_PRECOND_MULTILEVEL the coarse correction is itself a recursion over further aggregated levels (c8_krylov_multilevel.hpp,
 // DESIGN.md section 13e): block-sparse coarse matrices with sweeps of their own, the dense inverse on the last level only.
 //
@@ -622,7 +624,7 @@ template <int ND, int NRES, int G>
 Launchers launchers(int kind) {
   return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>,
                    kind == C8_PRECOND_MULTILEVEL ? launch_iteration_two_level<ND, NRES, G, true>
-                   : kind == C8_PRECOND_TWO_LEVEL ? launch_iteration_two_level<ND, NRES, G>
+                   : (kind == C8_PRECOND_TWO_LEVEL || kind == C8_PRECOND_TWO_LEVEL_PARTS) ? launch_iteration_two_level<ND, NRES, G>
                    : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>,
                    coarse_setup<ND, NRES, G>, multilevel_setup<ND, NRES, G>, G};
 }
@@ -949,15 +951,21 @@ void parts_iteration_sgs(Parts& P) {
   parts_scalars<2>(P, P.nb_upd);
 }
 
+#include "c8_krylov_parts_coarse.hpp"
+
 struct PartsLaunchers {
   void (*setup)(Parts&);
   void (*residual)(Parts&);
   void (*iteration)(Parts&);
+  void (*coarse)(Parts&, bool);  // the coarse level of the two-level kind over parts (parts_coarse_setup)
   int group;
 };
 template <int ND, int NRES, int G>
-PartsLaunchers parts_launchers(bool sgs) {
-  return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>, sgs ? parts_iteration_sgs<ND, NRES, G> : parts_iteration<ND, NRES, G>, G};
+PartsLaunchers parts_launchers(int kind) {
+  return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>,
+                        kind == C8_PRECOND_TWO_LEVEL_PARTS ? parts_iteration_two_level<ND, NRES, G>
+                        : kind == C8_PRECOND_BLOCK_SGS ? parts_iteration_sgs<ND, NRES, G> : parts_iteration<ND, NRES, G>,
+                        parts_coarse_setup<ND, NRES, G>, G};
 }
 
 // The host read of the scalars, COLLECTIVE: the ranks all-reduce (iterations, stop flag, their squares, failure marker).
@@ -1054,7 +1062,9 @@ int build_colors(c8_ctx* c) {
 template <int ND, int NRES, int G>
 int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  if (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS && c->halo) return precondition_parts<ND, NRES, G>(c, sys, v, y);  // (collective)
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
+  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Solve q{};
   q.c = c;
@@ -1148,7 +1158,9 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL, multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  // (no halo here: the kind over parts is the two-level kind)
+  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
+  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Launchers L;
   if (c->ndims == 3 && two) L = launchers<3, 2, 16>(c->kry_precond);
@@ -1278,11 +1290,12 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
 
   if (c->kry_precond == C8_PRECOND_TWO_LEVEL) return coarse_refusals(c, "c8_krylov_solve_parts");  // (a halo is attached: refused)
   if (c->kry_precond == C8_PRECOND_MULTILEVEL) return multilevel_refusals(c, "c8_krylov_solve_parts");
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS;
+  bool const coarse = c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse;
   PartsLaunchers L;
-  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(sgs);
-  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>(sgs);
-  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>(sgs);
+  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(c->kry_precond);
+  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>(c->kry_precond);
+  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>(c->kry_precond);
   else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve_parts: no kernels for this number of dimensions and residuals");
   int const nb = c->ndims + (two ? 1 : 0);
 
@@ -1299,6 +1312,10 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   P.nown = c8_halo_num_owned(c->halo);
   size_t const n0 = (size_t)q.nn * c->ndims;
   q.n = n0 + (two ? (size_t)q.nn : 0);
+  int rc;
+  // the two-level kind over parts: the cap on the global coarse size and the tables of the coarse level, before anything
+  // is assembled or iterated (collective at the first use; every rank returns the same code)
+  if (coarse && (rc = parts_coarse_prepare(c, P, "c8_krylov_solve_parts")) != C8_OK) return rc;
   // from here on every rank goes through the same sequence of collectives, whatever happens to it
   P.note(build_part_lists(c));
   if (sgs) P.note(build_colors(c));
@@ -1336,7 +1353,6 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   if (!P.failed) P.hip(hipMemsetAsync(vec, 0, 9 * q.n * sizeof(double), c->stream), "hipMemsetAsync");  // the copies' entries too
   L.setup(P);
   L.residual(P);
-  int rc;
   if ((rc = parts_read(P, &h)) != C8_OK) return rc;
   {  // the bad-node decision over the ranks: slot r holds rank r's smallest bad node + 1
     std::vector<double> bad(P.nranks, 0.);
@@ -1360,6 +1376,10 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   }
   double const tol = std::max(rel_tol * b_norm, abs_tol);
   q.tol2 = tol * tol;
+  if (coarse) {  // A_c = P^T A P over all parts and its inverse for this matrix, the outcome agreed over the ranks
+    L.coarse(P, true);
+    if ((rc = parts_coarse_agree(P, "c8_krylov_solve_parts")) != C8_OK) return rc;
+  }
 
   int restarts = 0, status = C8_NOT_CONVERGED;
   double true_norm = b_norm;
@@ -1407,7 +1427,8 @@ int c8_krylov_part_lists(c8_ctx* c, int32_t* num_interior, int32_t* num_boundary
 int c8_krylov_set_preconditioner(c8_ctx* c, int kind, int sweeps) {
   if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: null context");
   if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: a staged assembly is waiting for c8_gather_finish");
-  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL && kind != C8_PRECOND_MULTILEVEL)
+  if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL && kind != C8_PRECOND_MULTILEVEL &&
+      kind != C8_PRECOND_TWO_LEVEL_PARTS)
     return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: unknown preconditioner " + std::to_string(kind));
   c->kry_precond = kind;
   c->kry_sweeps = sweeps > 0 ? sweeps : 1;
@@ -1431,6 +1452,14 @@ int c8_krylov_colors(c8_ctx* c, int32_t* num_colors, const int32_t** color_ptr, 
 
 int c8_krylov_aggregates(c8_ctx* c, int32_t* num_aggregates, const int32_t** aggregate_of_node) {
   if (!c || !num_aggregates || !aggregate_of_node) return fail(C8_ERR_ARG, "c8_krylov_aggregates: null argument");
+  if (c->halo && c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS) {  // this rank's, by local id (collective at the first use)
+    Parts P = parts_of(c);
+    int const rcp = parts_aggregates(c, P);  // (reported above the cap of the coarse solve too)
+    if (rcp != C8_OK) return rcp;
+    *num_aggregates = c->kry_pc_nagg;
+    *aggregate_of_node = c->kry_pc_agg_of.data();
+    return C8_OK;
+  }
   if (c->halo) return coarse_refusals(c, "c8_krylov_aggregates");
   if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_aggregates: empty mesh");
   int const rc = build_aggregates(c);  // (reported above the cap of the coarse solve too)
@@ -1440,11 +1469,51 @@ int c8_krylov_aggregates(c8_ctx* c, int32_t* num_aggregates, const int32_t** agg
   return C8_OK;
 }
 
+int c8_krylov_aggregate_base(c8_ctx* c, int32_t* base, int32_t* total_aggregates) {
+  if (!c || !base || !total_aggregates) return fail(C8_ERR_ARG, "c8_krylov_aggregate_base: null argument");
+  if (!c->halo) {  // one part: its aggregates are all there are
+    if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_aggregate_base: empty mesh");
+    int const rc = build_aggregates(c);
+    if (rc != C8_OK) return rc;
+    *base = 0;
+    *total_aggregates = c->kry_nagg;
+    return C8_OK;
+  }
+  if (c->kry_precond != C8_PRECOND_TWO_LEVEL_PARTS)
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_aggregate_base: with a halo attached to the context only C8_PRECOND_TWO_LEVEL_PARTS has aggregates");
+  Parts P = parts_of(c);
+  int const rc = parts_aggregates(c, P);
+  if (rc != C8_OK) return rc;
+  if (c->kry_pc_total > INT_MAX) return fail(C8_ERR_UNSUPPORTED, "c8_krylov_aggregate_base: more than 2^31 aggregates");
+  *base = (int32_t)c->kry_pc_base;
+  *total_aggregates = (int32_t)c->kry_pc_total;
+  return C8_OK;
+}
+
 int c8_krylov_coarse_matrix(c8_ctx* c, const c8_system* sys, int32_t* n_coarse, double* out_host) {
   if (!c || !sys || !n_coarse) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null argument");
   bool const two = c->nres == 2;
   if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
     return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null array in the system");
+  if (c->halo && c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS) {  // collective: the global A_c, the same on every rank
+    Parts P = parts_of(c);
+    if (P.q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: empty mesh");
+    int rcp = out_host ? parts_coarse_prepare(c, P, "c8_krylov_coarse_matrix") : parts_coarse_refusals(c, P, "c8_krylov_coarse_matrix");
+    if (rcp != C8_OK) return rcp;
+    int const n = (int)c->kry_pc_total * coarse_columns(c), lda = (n + 1) & ~1;
+    *n_coarse = n;
+    if (!out_host) return C8_OK;
+    P.q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+    if (c->ndims == 3 && two) parts_coarse_setup<3, 2, 16>(P, false);
+    else if (c->ndims == 2 && two) parts_coarse_setup<2, 2, 8>(P, false);
+    else if (c->ndims == 2 && !two) parts_coarse_setup<2, 1, 8>(P, false);
+    else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_coarse_matrix: no kernels for this number of dimensions and residuals");
+    if (!P.failed)
+      P.hip(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
+                             hipMemcpyDeviceToHost, c->stream), "hipMemcpy2DAsync");
+    if (!P.failed) P.hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    return parts_coarse_agree(P, "c8_krylov_coarse_matrix");
+  }
   int rc = coarse_refusals(c, "c8_krylov_coarse_matrix");
   if (rc != C8_OK) return rc;
   int const n = c->kry_nagg * coarse_columns(c), lda = (n + 1) & ~1;

@@ -12,6 +12,7 @@ C8_KERNEL_AUTO, C8_KERNEL_SLOT, C8_KERNEL_WAVE, C8_KERNEL_WAVE_AD, C8_KERNEL_NOD
 C8_SCALE_NONE, C8_SCALE_LOG, C8_SCALE_BOUNDS = 0, 1, 2
 C8_PRECOND_BLOCK_JACOBI, C8_PRECOND_BLOCK_SGS, C8_PRECOND_TWO_LEVEL = 0, 1, 3  # (2 is not a kind: refused)
 C8_PRECOND_MULTILEVEL = 5  # (nor is 4)
+C8_PRECOND_TWO_LEVEL_PARTS = 7  # (nor is 6): the two-level kind with a coarse space over the parts of a multi-part mesh
 
 dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
@@ -187,6 +188,7 @@ SYMBOLS = [
     ("c8_krylov_get_preconditioner", C.c_int, [C.c_void_p]),
     ("c8_krylov_colors", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p), C.POINTER(i32p)]),
     ("c8_krylov_aggregates", C.c_int, [C.c_void_p, i32p, C.POINTER(i32p)]),
+    ("c8_krylov_aggregate_base", C.c_int, [C.c_void_p, i32p, i32p]),
     ("c8_krylov_coarse_matrix", C.c_int, [C.c_void_p, C.POINTER(System), i32p, dp]),
     ("c8_krylov_set_multilevel", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("c8_krylov_levels", C.c_int, [C.c_void_p, i32p]),

@@ -93,7 +93,9 @@ def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditione
     hence adjoint_gradient, InverseProblem and FEMUProblem over parts.  `asm` is the part's assembler, with its Halo attached
     before the first solve; every rank must make the same calls (the solve is collective).  preconditioner, sweeps and opts as
     for `device_solver`; "sgs" is part-local here (columns owned by other parts are dropped inside the sweeps); "two_level" and
-    "multilevel" cover one part only and the library refuses them here."""
+    "multilevel" cover one part only and the library refuses them here; "two_level_parts" is the two-level kind over parts
+    (C8_PRECOND_TWO_LEVEL_PARTS: aggregates per part, a dense coarse problem over all parts on every rank, capped at 8192
+    coarse unknowns in total; two more all-reduces per preconditioner apply)."""
     return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, preconditioner=preconditioner, sweeps=sweeps, **opts)
 
 

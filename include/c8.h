@@ -501,6 +501,40 @@ enum { C8_PRECOND_TWO_LEVEL = 3 };  /* 2 stays unassigned: callers have been tol
  * and the aggregate.  Every sum of the set-up and of the apply has a fixed order (no floating-point atomics); the inverse of
  * the last level comes from rocSOLVER as above. */
 enum { C8_PRECOND_MULTILEVEL = 5 };
+/* C8_PRECOND_TWO_LEVEL_PARTS is the two-level kind with a coarse space over the parts of a multi-part mesh: two levels, a
+ * dense coarse problem over ALL parts, replicated on every rank.  Without a halo it IS C8_PRECOND_TWO_LEVEL (the same
+ * launches); c8_krylov_solve keeps refusing a halo.  With a halo attached (c8_krylov_solve_parts; NC = 7, 4 or 3 as above):
+ *   aggregates   every rank runs the three passes above over its OWNED sub-graph: the first num_owned nodes, columns with
+ *             local id >= num_owned skipped (as the part-local colouring does).  No aggregate crosses a part boundary.
+ *             Global id = base_r + local id, base_r = the number of aggregates of the ranks below r; the counts travel in one
+ *             all-reduce of a vector with one slot per rank (each slot written by one rank: the sum is exact).  Centroid: the
+ *             unweighted mean of the member positions, summed in ascending local id.
+ *   P         the P above (rigid-body modes about the centroid, constant p), with rows for OWNED nodes only.  A row is zero
+ *             where its equation is constrained by the rule above, applied to the whole owned row after c8_halo_gather,
+ *             off-part columns included.  Never stored.
+ *   imported  the owner's P_j is needed at the ghost and phantom copies of node j: global aggregate id, offset from the
+ *             centroid, constrained flags.  They travel through the halo's owner -> copy (import) tables, the ones A x uses:
+ *             ids and offsets once per attached halo, flags at every set-up.  Copies are exact.
+ *   A_c       = P^T A P over all parts, dense, n_c = NC x (sum of the ranks' aggregates).  Rank r forms the block rows of its
+ *             own aggregates: every column j of an owned row contributes, ghost and phantom columns with the imported P_j;
+ *             the rows of other ranks are zero.  One all-reduce of the n_c^2 doubles gives every rank the same matrix: every
+ *             entry is one value plus zeros, so the result does not depend on the transport's order of summation, for any
+ *             number of parts.  A zero column of P gets a unit diagonal.  Every rank inverts its copy as above.  n_c must not
+ *             exceed 8192: above it every rank returns C8_ERR_UNSUPPORTED, the message names n_c and the cap, before anything
+ *             is assembled or iterated.
+ *   y = M^-1 v   r_c = P^T v: rank r fills the slots of its own aggregates, zeros elsewhere; one all-reduce of the n_c
+ *             doubles (exact for the same reason); e = A_c^-1 r_c for the rows of the rank's own aggregates; x = P e on the
+ *             owned nodes; then `sweeps` part-local symmetric sweeps (C8_PRECOND_BLOCK_SGS over parts) started from this x,
+ *             every colour launch over the owned columns.  A fixed linear operator.  An iteration of the solve makes two
+ *             imports and five all-reduces.
+ * A singular or non-finite A_c, a bad diagonal block, a device error on one rank and an aggregate with too many neighbouring
+ * aggregates for the kernel's tile are agreed over the ranks (one slot per rank in an all-reduced vector): every rank returns
+ * the same code.  With this kind selected and a halo attached, c8_krylov_aggregates returns the rank's LOCAL ids
+ * (aggregate_of_node[i], i < num_owned) and c8_krylov_aggregate_base the base; c8_krylov_coarse_matrix is COLLECTIVE and
+ * downloads the global A_c on every rank; c8_krylov_precondition is COLLECTIVE and applies the operator to the owned
+ * entries.  The first of these calls (or the first solve) after a halo is attached is collective too: it counts the
+ * aggregates over the ranks.  With the other coarse kinds selected all of them keep refusing a halo. */
+enum { C8_PRECOND_TWO_LEVEL_PARTS = 7 };  /* 6 stays unassigned, as 2 and 4 */
 int c8_krylov_set_preconditioner(c8_ctx* ctx, int kind, int sweeps);
 /* The two settings of C8_PRECOND_MULTILEVEL (<= 0: the default): coarse_max, default 1024 unknowns, and max_levels, default
  * 8, at least 2.  The levels are rebuilt at the next use.  C8_ERR_ARG for a null context, for max_levels = 1, and while a
@@ -515,6 +549,10 @@ int c8_krylov_colors(c8_ctx* ctx, int32_t* num_colors, const int32_t** color_ptr
  * use, freed by c8_destroy): aggregate_of_node[i] in [0, num_aggregates) for every node i.  Reported above the cap of the
  * coarse solve too.  C8_ERR_UNSUPPORTED with a halo attached. */
 int c8_krylov_aggregates(c8_ctx* ctx, int32_t* num_aggregates, const int32_t** aggregate_of_node);
+/* Diagnostic / test access: where this rank's aggregates start in the global numbering of C8_PRECOND_TWO_LEVEL_PARTS, and how
+ * many there are over all ranks (n_c = NC x total_aggregates).  Without a halo: 0 and the count of c8_krylov_aggregates.
+ * With a halo attached and another kind selected: C8_ERR_UNSUPPORTED. */
+int c8_krylov_aggregate_base(c8_ctx* ctx, int32_t* base, int32_t* total_aggregates);
 /* Diagnostic / test access: runs the set-up of C8_PRECOND_TWO_LEVEL on `sys` up to A_c = P^T A P (whatever kind is
  * selected) and copies the dense row-major n_coarse x n_coarse matrix to out_host (HOST memory); out_host NULL returns
  * n_coarse only.  C8_ERR_UNSUPPORTED with a halo attached or above the cap. */
