@@ -203,20 +203,24 @@ class Assembler:
         rigid-body modes of node aggregates, then `sweeps` of those sweeps; one part only) or "multilevel" (the same
         construction repeated on the coarse matrix, `sweeps` per level, set_krylov_multilevel; one part only) or
         "two_level_parts" (the two-level kind over the parts of a multi-part mesh: part-local aggregates, one dense coarse
-        problem over all parts replicated on every rank; "two_level" itself without a halo); c8_krylov_set_preconditioner."""
+        problem over all parts replicated on every rank; "two_level" itself without a halo) or "multilevel_parts" (the
+        multilevel kind over parts: the distributed level 0 of "two_level_parts" over block-sparse levels replicated on every
+        rank, no cap on the mesh, set_krylov_multilevel; "multilevel" itself without a halo); c8_krylov_set_preconditioner."""
         kinds = {"jacobi": _l.C8_PRECOND_BLOCK_JACOBI, "sgs": _l.C8_PRECOND_BLOCK_SGS, "two_level": _l.C8_PRECOND_TWO_LEVEL,
-                 "multilevel": _l.C8_PRECOND_MULTILEVEL, "two_level_parts": _l.C8_PRECOND_TWO_LEVEL_PARTS}
+                 "multilevel": _l.C8_PRECOND_MULTILEVEL, "two_level_parts": _l.C8_PRECOND_TWO_LEVEL_PARTS,
+                 "multilevel_parts": _l.C8_PRECOND_MULTILEVEL_PARTS}
         if kind not in kinds:
-            raise ValueError("preconditioner must be 'jacobi', 'sgs', 'two_level', 'multilevel' or 'two_level_parts', not %r" % (kind,))
+            raise ValueError("preconditioner must be 'jacobi', 'sgs', 'two_level', 'multilevel', 'two_level_parts' or 'multilevel_parts', not %r" % (kind,))
         _l.check(self.L.c8_krylov_set_preconditioner(self.h, kinds[kind], int(sweeps)))
 
     @property
     def krylov_preconditioner(self):
         return {_l.C8_PRECOND_BLOCK_JACOBI: "jacobi", _l.C8_PRECOND_BLOCK_SGS: "sgs", _l.C8_PRECOND_TWO_LEVEL: "two_level",
-                _l.C8_PRECOND_MULTILEVEL: "multilevel", _l.C8_PRECOND_TWO_LEVEL_PARTS: "two_level_parts"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
+                _l.C8_PRECOND_MULTILEVEL: "multilevel", _l.C8_PRECOND_TWO_LEVEL_PARTS: "two_level_parts",
+                _l.C8_PRECOND_MULTILEVEL_PARTS: "multilevel_parts"}[_l.check(self.L.c8_krylov_get_preconditioner(self.h))]
 
     def set_krylov_multilevel(self, coarse_max=None, max_levels=None):
-        """Settings of the "multilevel" preconditioner: another level is built while the coarsest one has more than
+        """Settings of the "multilevel" and "multilevel_parts" preconditioners: another level is built while the coarsest one has more than
         `coarse_max` unknowns and fewer than `max_levels` levels exist (the system counts as one); None: the library's
         default.  The levels are rebuilt at the next solve; c8_krylov_set_multilevel."""
         _l.check(self.L.c8_krylov_set_multilevel(self.h, int(coarse_max or 0), int(max_levels or 0)))

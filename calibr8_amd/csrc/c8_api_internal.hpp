@@ -165,6 +165,14 @@ struct c8_ctx {
   double* d_kry_pc_off = nullptr;    // [nnodes][ndims], the copies' entries imported from their owners
   int32_t* d_kry_pc_flags = nullptr; // [nnodes] constrained-row flags of the current matrix, the copies' imported
   double* d_kry_pc_imp = nullptr;    // a vector's worth of doubles: what the import tables move the ids and the flags in
+  // ... the levels of C8_PRECOND_MULTILEVEL_PARTS below level 0 (c8_krylov_parts_multilevel.hpp): level 1 is the graph of
+  // the aggregates of all ranks, replicated on every rank from the lists below; a list of its own, so that switching
+  // between the kinds rebuilds neither
+  std::vector<int32_t> kry_pc_nbr_ptr, kry_pc_nbr;  // neighbouring aggregates (GLOBAL ids, ascending) of this rank's aggregates
+  std::vector<double> kry_pc_x;      // [kry_pc_nagg][3] centroids of this rank's aggregates
+  int kry_pl_for = -1;               // num_owned the levels were built for (-1: not built; reset by c8_halo_attach and c8_krylov_set_multilevel)
+  double kry_pl_bad = -1.;           // finding of the last set-up: level * 2^32 + block or row (-1: none)
+  std::vector<c8_kry_level> kry_pl_levels;            // [k] is level k + 1; freed by c8_krylov_release
 };
 void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)

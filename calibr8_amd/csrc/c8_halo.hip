@@ -643,7 +643,7 @@ int c8_halo_attach(c8_halo* h, c8_ctx* c, c8_comm* cm) {
   h->comm = cm;
   c->halo = h;
   c->num_parts = cm->nranks;
-  c->kry_pc_host_for = -1, c->kry_pc_for = -1;  // the aggregates over parts and their imported data belong to one attached halo
+  c->kry_pc_host_for = -1, c->kry_pc_for = -1, c->kry_pl_for = -1;  // the aggregates over parts and their imported data belong to one attached halo
   return C8_OK;
 }
 

@@ -24,6 +24,8 @@
 // (DESIGN.md section 13f): part-local aggregates, a dense global A_c replicated on every rank, two more all-reduces per apply.
 // With C8_PRECOND_MULTILEVEL the coarse correction is itself a recursion over further aggregated levels (c8_krylov_multilevel.hpp,
 // DESIGN.md section 13e): block-sparse coarse matrices with sweeps of their own, the dense inverse on the last level only.
+// C8_PRECOND_MULTILEVEL_PARTS is that kind without a halo; over parts it keeps the distributed level 0 of the two-level kind
+// over parts and runs the levels from 1 down replicated on every rank (c8_krylov_parts_multilevel.hpp).
 //
 // Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
 // the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
@@ -623,7 +625,7 @@ struct Launchers {
 template <int ND, int NRES, int G>
 Launchers launchers(int kind) {
   return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>,
-                   kind == C8_PRECOND_MULTILEVEL ? launch_iteration_two_level<ND, NRES, G, true>
+                   (kind == C8_PRECOND_MULTILEVEL || kind == C8_PRECOND_MULTILEVEL_PARTS) ? launch_iteration_two_level<ND, NRES, G, true>
                    : (kind == C8_PRECOND_TWO_LEVEL || kind == C8_PRECOND_TWO_LEVEL_PARTS) ? launch_iteration_two_level<ND, NRES, G>
                    : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>,
                    coarse_setup<ND, NRES, G>, multilevel_setup<ND, NRES, G>, G};
@@ -952,20 +954,23 @@ void parts_iteration_sgs(Parts& P) {
 }
 
 #include "c8_krylov_parts_coarse.hpp"
+#include "c8_krylov_parts_multilevel.hpp"
 
 struct PartsLaunchers {
   void (*setup)(Parts&);
   void (*residual)(Parts&);
   void (*iteration)(Parts&);
   void (*coarse)(Parts&, bool);  // the coarse level of the two-level kind over parts (parts_coarse_setup)
+  void (*levels)(Parts&, int);   // the hierarchy of the multilevel kind over parts (parts_levels_setup)
   int group;
 };
 template <int ND, int NRES, int G>
 PartsLaunchers parts_launchers(int kind) {
   return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>,
-                        kind == C8_PRECOND_TWO_LEVEL_PARTS ? parts_iteration_two_level<ND, NRES, G>
+                        kind == C8_PRECOND_MULTILEVEL_PARTS ? parts_iteration_multilevel<ND, NRES, G>
+                        : kind == C8_PRECOND_TWO_LEVEL_PARTS ? parts_iteration_two_level<ND, NRES, G>
                         : kind == C8_PRECOND_BLOCK_SGS ? parts_iteration_sgs<ND, NRES, G> : parts_iteration<ND, NRES, G>,
-                        parts_coarse_setup<ND, NRES, G>, G};
+                        parts_coarse_setup<ND, NRES, G>, parts_levels_setup<ND, NRES, G>, G};
 }
 
 // The host read of the scalars, COLLECTIVE: the ranks all-reduce (iterations, stop flag, their squares, failure marker).
@@ -1062,9 +1067,10 @@ int build_colors(c8_ctx* c) {
 template <int ND, int NRES, int G>
 int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
-  if (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS && c->halo) return precondition_parts<ND, NRES, G>(c, sys, v, y);  // (collective)
+  if ((c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) && c->halo)
+    return precondition_parts<ND, NRES, G>(c, sys, v, y);  // (collective)
   bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
-  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Solve q{};
   q.c = c;
@@ -1158,9 +1164,9 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const rel_tol = (opts && opts->rel_tol > 0.) ? opts->rel_tol : 1e-10;
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
-  // (no halo here: the kind over parts is the two-level kind)
+  // (no halo here: a kind over parts is the kind of one part)
   bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
-  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL;
+  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
   bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
   Launchers L;
   if (c->ndims == 3 && two) L = launchers<3, 2, 16>(c->kry_precond);
@@ -1290,8 +1296,8 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
 
   if (c->kry_precond == C8_PRECOND_TWO_LEVEL) return coarse_refusals(c, "c8_krylov_solve_parts");  // (a halo is attached: refused)
   if (c->kry_precond == C8_PRECOND_MULTILEVEL) return multilevel_refusals(c, "c8_krylov_solve_parts");
-  bool const coarse = c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse;
+  bool const coarse = c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS, multi = c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse || multi;
   PartsLaunchers L;
   if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(c->kry_precond);
   else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>(c->kry_precond);
@@ -1316,6 +1322,8 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   // the two-level kind over parts: the cap on the global coarse size and the tables of the coarse level, before anything
   // is assembled or iterated (collective at the first use; every rank returns the same code)
   if (coarse && (rc = parts_coarse_prepare(c, P, "c8_krylov_solve_parts")) != C8_OK) return rc;
+  // the multilevel kind over parts: the replicated levels and the cap on the last of them, in the same place
+  if (multi && (rc = parts_levels_prepare(c, P, "c8_krylov_solve_parts")) != C8_OK) return rc;
   // from here on every rank goes through the same sequence of collectives, whatever happens to it
   P.note(build_part_lists(c));
   if (sgs) P.note(build_colors(c));
@@ -1380,6 +1388,10 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
     L.coarse(P, true);
     if ((rc = parts_coarse_agree(P, "c8_krylov_solve_parts")) != C8_OK) return rc;
   }
+  if (multi) {  // A_1 over all parts, every A_l below it and the inverse of the last one, the outcome agreed over the ranks
+    L.levels(P, -1);
+    if ((rc = parts_levels_agree(P, "c8_krylov_solve_parts")) != C8_OK) return rc;
+  }
 
   int restarts = 0, status = C8_NOT_CONVERGED;
   double true_norm = b_norm;
@@ -1428,7 +1440,7 @@ int c8_krylov_set_preconditioner(c8_ctx* c, int kind, int sweeps) {
   if (!c) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: null context");
   if (c->gather_pending) return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: a staged assembly is waiting for c8_gather_finish");
   if (kind != C8_PRECOND_BLOCK_JACOBI && kind != C8_PRECOND_BLOCK_SGS && kind != C8_PRECOND_TWO_LEVEL && kind != C8_PRECOND_MULTILEVEL &&
-      kind != C8_PRECOND_TWO_LEVEL_PARTS)
+      kind != C8_PRECOND_TWO_LEVEL_PARTS && kind != C8_PRECOND_MULTILEVEL_PARTS)
     return fail(C8_ERR_ARG, "c8_krylov_set_preconditioner: unknown preconditioner " + std::to_string(kind));
   c->kry_precond = kind;
   c->kry_sweeps = sweeps > 0 ? sweeps : 1;
@@ -1452,7 +1464,7 @@ int c8_krylov_colors(c8_ctx* c, int32_t* num_colors, const int32_t** color_ptr, 
 
 int c8_krylov_aggregates(c8_ctx* c, int32_t* num_aggregates, const int32_t** aggregate_of_node) {
   if (!c || !num_aggregates || !aggregate_of_node) return fail(C8_ERR_ARG, "c8_krylov_aggregates: null argument");
-  if (c->halo && c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS) {  // this rank's, by local id (collective at the first use)
+  if (c->halo && (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS)) {  // this rank's, by local id (collective at the first use)
     Parts P = parts_of(c);
     int const rcp = parts_aggregates(c, P);  // (reported above the cap of the coarse solve too)
     if (rcp != C8_OK) return rcp;
@@ -1479,8 +1491,9 @@ int c8_krylov_aggregate_base(c8_ctx* c, int32_t* base, int32_t* total_aggregates
     *total_aggregates = c->kry_nagg;
     return C8_OK;
   }
-  if (c->kry_precond != C8_PRECOND_TWO_LEVEL_PARTS)
-    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_aggregate_base: with a halo attached to the context only C8_PRECOND_TWO_LEVEL_PARTS has aggregates");
+  if (c->kry_precond != C8_PRECOND_TWO_LEVEL_PARTS && c->kry_precond != C8_PRECOND_MULTILEVEL_PARTS)
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_aggregate_base: with a halo attached to the context only C8_PRECOND_TWO_LEVEL_PARTS and "
+                                    "C8_PRECOND_MULTILEVEL_PARTS have aggregates");
   Parts P = parts_of(c);
   int const rc = parts_aggregates(c, P);
   if (rc != C8_OK) return rc;
@@ -1495,7 +1508,7 @@ int c8_krylov_coarse_matrix(c8_ctx* c, const c8_system* sys, int32_t* n_coarse, 
   bool const two = c->nres == 2;
   if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
     return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null array in the system");
-  if (c->halo && c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS) {  // collective: the global A_c, the same on every rank
+  if (c->halo && (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS)) {  // collective: the global A_c, the same on every rank
     Parts P = parts_of(c);
     if (P.q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: empty mesh");
     int rcp = out_host ? parts_coarse_prepare(c, P, "c8_krylov_coarse_matrix") : parts_coarse_refusals(c, P, "c8_krylov_coarse_matrix");
@@ -1540,12 +1553,20 @@ int c8_krylov_set_multilevel(c8_ctx* c, int32_t coarse_max, int32_t max_levels) 
   if (max_levels == 1) return fail(C8_ERR_ARG, "c8_krylov_set_multilevel: max_levels counts level 0 and must be at least 2");
   c->kry_ml_coarse_max = coarse_max > 0 ? coarse_max : 0;
   c->kry_ml_max_levels = max_levels > 0 ? max_levels : 0;
-  c->kry_ml_built = false;  // the levels are rebuilt at the next use
+  c->kry_ml_built = false;  // the levels are rebuilt at the next use, of one part ...
+  c->kry_pl_for = -1;       // ... and over parts
   return C8_OK;
 }
 
 int c8_krylov_levels(c8_ctx* c, int32_t* num_levels) {
   if (!c || !num_levels) return fail(C8_ERR_ARG, "c8_krylov_levels: null argument");
+  if (c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) {  // collective at the first use (reported above the cap too)
+    Parts P = parts_of(c);
+    int const rcp = parts_levels_build(c, P, "c8_krylov_levels");
+    if (rcp != C8_OK) return rcp;
+    *num_levels = (int32_t)c->kry_pl_levels.size() + 1;
+    return C8_OK;
+  }
   if (c->halo) return multilevel_refusals(c, "c8_krylov_levels");
   if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_levels: empty mesh");
   int const rc = build_levels(c);  // (reported with a last level above the cap too)
@@ -1557,22 +1578,28 @@ int c8_krylov_levels(c8_ctx* c, int32_t* num_levels) {
 int c8_krylov_level(c8_ctx* c, int32_t level, int32_t* num_nodes, const int32_t** aggregate_of_node, int32_t* num_colors,
                     const int32_t** color_ptr, const int32_t** nodes) {
   if (!c || !num_nodes || !aggregate_of_node || !num_colors || !color_ptr || !nodes) return fail(C8_ERR_ARG, "c8_krylov_level: null argument");
-  if (c->halo) return multilevel_refusals(c, "c8_krylov_level");
+  bool const parts = c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;  // the rank's own level 0, the replicated levels below
+  if (c->halo && !parts) return multilevel_refusals(c, "c8_krylov_level");
   if (c->mesh.nnodes <= 0) return fail(C8_ERR_ARG, "c8_krylov_level: empty mesh");
-  int rc = build_levels(c);
+  int rc;
+  if (parts) {  // (collective at the first use)
+    Parts P = parts_of(c);
+    rc = parts_levels_build(c, P, "c8_krylov_level");
+  } else rc = build_levels(c);
   if (rc != C8_OK) return rc;
-  int const nl = (int)c->kry_levels.size();
+  std::vector<c8_kry_level> const& lv = parts ? c->kry_pl_levels : c->kry_levels;
+  int const nl = (int)lv.size();
   if (level < 0 || level > nl) return fail(C8_ERR_ARG, "c8_krylov_level: level " + std::to_string(level) + " of " + std::to_string(nl + 1));
   if (level == 0) {
     if ((rc = build_colors(c)) != C8_OK) return rc;
-    *num_nodes = c->mesh.nnodes;
-    *aggregate_of_node = c->kry_agg_of.data();
+    *num_nodes = parts ? c8_halo_num_owned(c->halo) : c->mesh.nnodes;
+    *aggregate_of_node = parts ? c->kry_pc_agg_of.data() : c->kry_agg_of.data();
     *num_colors = (int32_t)c->kry_color_ptr.size() - 1;
     *color_ptr = c->kry_color_ptr.data();
     *nodes = c->kry_color_nodes.data();
     return C8_OK;
   }
-  c8_kry_level const& L = c->kry_levels[level - 1];
+  c8_kry_level const& L = lv[level - 1];
   bool const last = level == nl;  // dense: no aggregates and no sweeps
   *num_nodes = L.n;
   *aggregate_of_node = last ? nullptr : L.agg_of.data();
@@ -1587,6 +1614,7 @@ int c8_krylov_level_matrix(c8_ctx* c, const c8_system* sys, int32_t level, int32
   bool const two = c->nres == 2;
   if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
     return fail(C8_ERR_ARG, "c8_krylov_level_matrix: null array in the system");
+  if (c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) return parts_level_matrix(c, sys, level, n_level, out_host);  // (collective)
   int rc = multilevel_refusals(c, "c8_krylov_level_matrix");
   if (rc != C8_OK) return rc;
   int const nl = (int)c->kry_levels.size(), nc = coarse_columns(c);
@@ -1642,6 +1670,7 @@ int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const 
 
 void c8_krylov_release(c8_ctx* c) {
   free_levels(c);
+  free_level_list(c->kry_pl_levels);
   if (c->kry_rocblas) (void)rocblas_destroy_handle((rocblas_handle)c->kry_rocblas);
   c->kry_rocblas = nullptr;
 }

@@ -282,13 +282,16 @@ constexpr int ML_MAX_LEVELS = 8;
 inline int ml_coarse_max(c8_ctx const* c) { return c->kry_ml_coarse_max > 0 ? c->kry_ml_coarse_max : ML_COARSE_MAX; }
 inline int ml_max_levels(c8_ctx const* c) { return c->kry_ml_max_levels > 0 ? c->kry_ml_max_levels : ML_MAX_LEVELS; }
 
-void free_levels(c8_ctx* c) {
-  for (c8_kry_level& L : c->kry_levels) {
+void free_level_list(std::vector<c8_kry_level>& lv) {
+  for (c8_kry_level& L : lv) {
     void* bufs[] = {L.d_graph, L.d_agg, L.d_off, L.d_flags, L.d_colors, L.d_A, L.d_minv, L.d_vec};
     for (void* b : bufs)
       if (b) (void)hipFree(b);
   }
-  c->kry_levels.clear();
+  lv.clear();
+}
+void free_levels(c8_ctx* c) {
+  free_level_list(c->kry_levels);
   c->kry_ml_built = false;
 }
 
@@ -301,23 +304,14 @@ int upload(T** dst, std::vector<T> const& src) {
   return C8_OK;
 }
 
-// The levels below level 0 from the aggregates of level 0, once per setting of c8_krylov_set_multilevel: kry_levels[k] is
-// level k + 1.  Level 1 always exists (P_0 is the P of the two-level kind); another level is built while the last one has
-// more than coarse_max unknowns, fewer than max_levels levels exist and aggregation still reduces the node count.
-int build_levels(c8_ctx* c) {
-  if (c->kry_ml_built) return C8_OK;
-  free_levels(c);
-  int rc = build_aggregates(c);
-  if (rc != C8_OK) return rc;
+// The levels below level 1 of a list that holds level 1 as (n, graph, positions): lv[k] is level k + 1.  Another level is
+// built while the last one has more than coarse_max unknowns, fewer than max_levels levels exist (level 0 counts) and
+// aggregation still reduces the node count.  Host rules only: the same list in gives the same levels out.
+int extend_levels(c8_ctx* c, std::vector<c8_kry_level>& lv) {
   int const nd = c->ndims, nc = coarse_columns(c);
-  c->kry_levels.emplace_back();
-  {
-    c8_kry_level& L1 = c->kry_levels.back();
-    L1.n = c->kry_nagg;
-    L1.gp = c->kry_agg_nbr_ptr, L1.ga = c->kry_agg_nbr, L1.x = c->kry_agg_x;
-  }
-  while ((long long)c->kry_levels.back().n * nc > ml_coarse_max(c) && (int)c->kry_levels.size() + 1 < ml_max_levels(c)) {
-    c8_kry_level& L = c->kry_levels.back();
+  int rc;
+  while ((long long)lv.back().n * nc > ml_coarse_max(c) && (int)lv.size() + 1 < ml_max_levels(c)) {
+    c8_kry_level& L = lv.back();
     Aggregates H = aggregate_graph(L.n, nd, L.gp, L.ga, L.x.data());
     if (H.nagg >= L.n) break;
     L.nagg = H.nagg, L.max_nbr = H.max_nbr, L.agg_of = H.agg;
@@ -335,8 +329,25 @@ int build_levels(c8_ctx* c) {
     c8_kry_level next;
     next.n = H.nagg;
     next.gp = std::move(H.nbr_ptr), next.ga = std::move(H.nbr), next.x = std::move(H.centroid);
-    c->kry_levels.push_back(std::move(next));
+    lv.push_back(std::move(next));
   }
+  return C8_OK;
+}
+
+// The levels below level 0 from the aggregates of level 0, once per setting of c8_krylov_set_multilevel: kry_levels[k] is
+// level k + 1.  Level 1 always exists (P_0 is the P of the two-level kind); the levels below it by extend_levels.
+int build_levels(c8_ctx* c) {
+  if (c->kry_ml_built) return C8_OK;
+  free_levels(c);
+  int rc = build_aggregates(c);
+  if (rc != C8_OK) return rc;
+  c->kry_levels.emplace_back();
+  {
+    c8_kry_level& L1 = c->kry_levels.back();
+    L1.n = c->kry_nagg;
+    L1.gp = c->kry_agg_nbr_ptr, L1.ga = c->kry_agg_nbr, L1.x = c->kry_agg_x;
+  }
+  if ((rc = extend_levels(c, c->kry_levels)) != C8_OK) return rc;
   c->kry_ml_built = true;
   return C8_OK;
 }
@@ -369,6 +380,62 @@ int multilevel_refusals(c8_ctx* c, char const* who) {
   return C8_OK;
 }
 
+// The numeric set-up of a list of levels (lv[k] is level k + 1, the last one dense) in three steps, shared by the kind over
+// one part and the kind over parts (c8_krylov_parts_multilevel.hpp), which differ in how A_1 is formed between the first
+// two.  levels_begin: the buffers of the last level and the status words `info` (getrf, getri, first row of the inverse
+// that is not finite, then per level k + 1 its bad block), r_c and e zeroed.
+template <int NC>
+int levels_begin(c8_ctx* c, std::vector<c8_kry_level> const& lv, std::vector<int32_t>* h_info, int32_t** info) {
+  int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1;
+  int rc;
+  if ((rc = grow(&c->d_kry_Ac, &c->kry_Ac_n, (size_t)n * lda)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_cvec, &c->kry_cvec_n, 2 * (size_t)lda)) != C8_OK) return rc;
+  if ((rc = grow(&c->d_kry_ipiv, &c->kry_ipiv_n, (size_t)n + 4 + nl)) != C8_OK) return rc;
+  *info = c->d_kry_ipiv + n;
+  h_info->assign(3 + nl, INT_MAX);
+  (*h_info)[0] = (*h_info)[1] = 0;
+  C8_HIP(hipMemcpyAsync(*info, h_info->data(), h_info->size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  C8_HIP(hipMemsetAsync(c->d_kry_cvec, 0, 2 * (size_t)lda * sizeof(double), c->stream));
+  return C8_OK;
+}
+
+// levels_form: with A_1 in place, level k + 1 -> level k + 2 for every level up to `upto` (k_level_setup, k_level_galerkin)
+template <int ND, int NRES>
+int levels_form(c8_ctx* c, std::vector<c8_kry_level> const& lv, int upto, int32_t* info) {
+  constexpr int NC = CoarseDims<ND, NRES>::NC;
+  int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1;
+  hipStream_t const st = c->stream;
+  for (int k = 0; k + 1 < nl && k + 1 < upto; ++k) {
+    c8_kry_level const& L = lv[k];
+    hipLaunchKernelGGL((k_level_setup<NC>), dim3((L.n + TPB - 1) / TPB), dim3(TPB), 0, st, level_tables(L), L.d_minv, L.d_flags, info + 3 + k);
+    C8_HIP(hipGetLastError());
+    size_t const lds = (size_t)L.max_nbr * NC * NC * sizeof(double);
+    if (k + 2 == nl)
+      hipLaunchKernelGGL((k_level_galerkin<ND, NRES, true>), dim3(L.nagg), dim3(TPB), lds, st, level_agg_tables(L), level_tables(L), c->d_kry_Ac, lda);
+    else
+      hipLaunchKernelGGL((k_level_galerkin<ND, NRES, false>), dim3(L.nagg), dim3(TPB), lds, st, level_agg_tables(L), level_tables(L), lv[k + 1].d_A, 0);
+    C8_HIP(hipGetLastError());
+  }
+  return C8_OK;
+}
+
+// levels_invert: the checked inverse of the last level; the status words come back in h_info (a host read)
+template <int NC>
+int levels_invert(c8_ctx* c, std::vector<c8_kry_level> const& lv, int32_t* info, std::vector<int32_t>* h_info) {
+  int const n = lv.back().n * NC, lda = (n + 1) & ~1;
+  hipStream_t const st = c->stream;
+  int rc;
+  if ((rc = coarse_invert(c, n, lda, c->d_kry_Ac, c->d_kry_ipiv, info)) != C8_OK) return rc;
+  int const nb_c = (int)std::min<size_t>(((size_t)n * lda + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_coarse_check, dim3(nb_c), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, info + 2);
+  C8_HIP(hipGetLastError());
+  C8_HIP(hipMemcpyAsync(h_info->data(), info, h_info->size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  C8_HIP(hipStreamSynchronize(st));
+  return C8_OK;
+}
+// ... the bad row of the last level in those words (-1: none)
+inline int levels_bad_row(std::vector<int32_t> const& h) { return h[0] > 0 ? h[0] - 1 : h[1] > 0 ? h[1] - 1 : h[2] != INT_MAX ? h[2] : -1; }
+
 // The hierarchy for the matrix of q: A_1 .. A_upto (upto < 0: all levels, then the checked inverse of the last one).
 // Needs multilevel_refusals() passed.
 template <int ND, int NRES, int G>
@@ -386,56 +453,65 @@ int multilevel_setup(Solve const& q, int upto) {
     return fail(C8_ERR_UNSUPPORTED, "c8_krylov: an aggregate has " + std::to_string(worst) +
                                     " neighbouring aggregates: the block row of a coarse matrix does not fit the tile of k_galerkin");
   int rc;
-  if ((rc = grow(&c->d_kry_Ac, &c->kry_Ac_n, (size_t)n * lda)) != C8_OK) return rc;
-  if ((rc = grow(&c->d_kry_cvec, &c->kry_cvec_n, 2 * (size_t)lda)) != C8_OK) return rc;
-  if ((rc = grow(&c->d_kry_ipiv, &c->kry_ipiv_n, (size_t)n + 4 + nl)) != C8_OK) return rc;
   hipStream_t const st = c->stream;
-  int32_t* info = c->d_kry_ipiv + n;  // getrf, getri, first row of the inverse that is not finite, then per level k + 1 its bad block
-  std::vector<int32_t> h_info(3 + nl, INT_MAX);
-  h_info[0] = h_info[1] = 0;
-  C8_HIP(hipMemcpyAsync(info, h_info.data(), h_info.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  C8_HIP(hipMemsetAsync(c->d_kry_cvec, 0, 2 * (size_t)lda * sizeof(double), st));
+  int32_t* info = nullptr;
+  std::vector<int32_t> h_info;
+  if ((rc = levels_begin<NC>(c, lv, &h_info, &info)) != C8_OK) return rc;
   int const nb_g = (q.nn + TPB / G - 1) / (TPB / G);
   hipLaunchKernelGGL((k_constrained<ND, NRES, G>), dim3(xcd_grid(nb_g)), dim3(TPB), 0, st, q.nn, nb_g, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_cflags);
   C8_HIP(hipGetLastError());
   if (nl == 1 || upto >= nl) C8_HIP(hipMemsetAsync(c->d_kry_Ac, 0, (size_t)n * lda * sizeof(double), st));
-  size_t lds = (size_t)c->kry_agg_max_nbr * NC * NC * sizeof(double);
+  size_t const lds = (size_t)c->kry_agg_max_nbr * NC * NC * sizeof(double);
   if (nl == 1)
     hipLaunchKernelGGL((k_galerkin<ND, NRES, false>), dim3(c->kry_nagg), dim3(TPB), lds, st, agg_tables(c), c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_Ac, lda);
   else
     hipLaunchKernelGGL((k_galerkin<ND, NRES, true>), dim3(c->kry_nagg), dim3(TPB), lds, st, agg_tables(c), c->d_nodeptr, c->d_nodeadj, q.A, lv[0].d_A, 0);
   C8_HIP(hipGetLastError());
-  for (int k = 0; k + 1 < nl && k + 1 < upto; ++k) {  // level k + 1 -> level k + 2
-    c8_kry_level const& L = lv[k];
-    hipLaunchKernelGGL((k_level_setup<NC>), dim3((L.n + TPB - 1) / TPB), dim3(TPB), 0, st, level_tables(L), L.d_minv, L.d_flags, info + 3 + k);
-    C8_HIP(hipGetLastError());
-    lds = (size_t)L.max_nbr * NC * NC * sizeof(double);
-    if (k + 2 == nl)
-      hipLaunchKernelGGL((k_level_galerkin<ND, NRES, true>), dim3(L.nagg), dim3(TPB), lds, st, level_agg_tables(L), level_tables(L), c->d_kry_Ac, lda);
-    else
-      hipLaunchKernelGGL((k_level_galerkin<ND, NRES, false>), dim3(L.nagg), dim3(TPB), lds, st, level_agg_tables(L), level_tables(L), lv[k + 1].d_A, 0);
-    C8_HIP(hipGetLastError());
-  }
+  if ((rc = levels_form<ND, NRES>(c, lv, upto, info)) != C8_OK) return rc;
   if (!invert) return C8_OK;
-  if ((rc = coarse_invert(c, n, lda, c->d_kry_Ac, c->d_kry_ipiv, info)) != C8_OK) return rc;
-  int const nb_c = (int)std::min<size_t>(((size_t)n * lda + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_coarse_check, dim3(nb_c), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, info + 2);
-  C8_HIP(hipGetLastError());
-  C8_HIP(hipMemcpyAsync(h_info.data(), info, h_info.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  C8_HIP(hipStreamSynchronize(st));
+  if ((rc = levels_invert<NC>(c, lv, info, &h_info)) != C8_OK) return rc;
   for (int k = 0; k + 1 < nl; ++k)
     if (h_info[3 + k] != INT_MAX)
       return fail(C8_ERR_ARG, "c8_krylov: the diagonal block of aggregate " + std::to_string(h_info[3 + k]) + " on level " + std::to_string(k + 1) +
                               " of the multilevel preconditioner is singular or not finite");
-  int const bad = h_info[0] > 0 ? h_info[0] - 1 : h_info[1] > 0 ? h_info[1] - 1 : h_info[2] != INT_MAX ? h_info[2] : -1;
+  int const bad = levels_bad_row(h_info);
   if (bad >= 0)
     return fail(C8_ERR_ARG, "c8_krylov: the matrix of level " + std::to_string(nl) + " (the last) of the multilevel preconditioner is singular or not finite at aggregate " +
                             std::to_string(bad / NC) + " (row " + std::to_string(bad) + " of " + std::to_string(n) + ")");
   return C8_OK;
 }
 
-// x = P_0 M_1^-1 P_0^T rhs: down the levels, the dense solve, up again with the sweeps of every block level; the caller's
-// sweeps on level 0 start from this x
+// e_1 = M_1^-1 r_1 on a list of levels, r_1 and e_1 in the two halves of level 1's vector (of d_kry_cvec when level 1 is the
+// last): down the levels, the dense solve, up again with the sweeps of every block level, level 1 included
+template <int ND, int NRES>
+hipError_t launch_level_cycle(c8_ctx const* c, std::vector<c8_kry_level> const& lv, KryScalars const* S) {
+  constexpr int NC = CoarseDims<ND, NRES>::NC;
+  int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1, wpb = TPB / 64;
+  hipStream_t const st = c->stream;
+  auto rhs_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec : lv[k].d_vec; };  // of level k + 1
+  auto x_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec + lda : lv[k].d_vec + (size_t)lv[k].n * NC; };
+  for (int k = 0; k + 1 < nl; ++k)
+    hipLaunchKernelGGL((k_level_restrict<ND, NRES>), dim3((lv[k].nagg + wpb - 1) / wpb), dim3(TPB), 0, st, lv[k].nagg, level_agg_tables(lv[k]), rhs_of(k),
+                       rhs_of(k + 1), S);
+  hipLaunchKernelGGL(k_coarse_apply, dim3((n + wpb - 1) / wpb), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, rhs_of(nl - 1), x_of(nl - 1), S);
+  for (int k = nl - 2; k >= 0; --k) {
+    c8_kry_level const& L = lv[k];
+    hipLaunchKernelGGL((k_level_prolong<ND, NRES>), dim3((L.n + TPB - 1) / TPB), dim3(TPB), 0, st, L.n, level_agg_tables(L), x_of(k + 1), x_of(k), S);
+    int const ncol = (int)L.color_ptr.size() - 1;
+    auto color = [&](int j) {
+      int const lo = L.color_ptr[j], m = L.color_ptr[j + 1] - lo, npb = TPB / LEVEL_G;
+      hipLaunchKernelGGL((k_level_sgs<NC>), dim3((m + npb - 1) / npb), dim3(TPB), 0, st, L.d_colors + lo, m, level_tables(L), L.d_minv, rhs_of(k), x_of(k), S);
+    };
+    for (int s = 0; s < c->kry_sweeps; ++s) {
+      for (int j = 0; j < ncol; ++j) color(j);
+      for (int j = ncol - 2; j >= 0; --j) color(j);
+    }
+  }
+  return hipGetLastError();
+}
+
+// x = P_0 M_1^-1 P_0^T rhs: k_restrict, the cycle over the levels, k_prolong; the caller's sweeps on level 0 start from
+// this x
 template <int ND, int NRES>
 hipError_t launch_multilevel(Solve const& q, double const* rhs, double* x) {
   constexpr int NC = CoarseDims<ND, NRES>::NC;
@@ -443,26 +519,11 @@ hipError_t launch_multilevel(Solve const& q, double const* rhs, double* x) {
   std::vector<c8_kry_level> const& lv = c->kry_levels;
   int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1, wpb = TPB / 64;
   hipStream_t const st = c->stream;
-  auto rhs_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec : lv[k].d_vec; };  // of level k + 1
-  auto x_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec + lda : lv[k].d_vec + (size_t)lv[k].n * NC; };
-  hipLaunchKernelGGL((k_restrict<ND, NRES>), dim3((c->kry_nagg + wpb - 1) / wpb), dim3(TPB), 0, st, c->kry_nagg, agg_tables(c), q.nn, rhs, rhs_of(0), q.S);
-  for (int k = 0; k + 1 < nl; ++k)
-    hipLaunchKernelGGL((k_level_restrict<ND, NRES>), dim3((lv[k].nagg + wpb - 1) / wpb), dim3(TPB), 0, st, lv[k].nagg, level_agg_tables(lv[k]), rhs_of(k),
-                       rhs_of(k + 1), q.S);
-  hipLaunchKernelGGL(k_coarse_apply, dim3((n + wpb - 1) / wpb), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, rhs_of(nl - 1), x_of(nl - 1), q.S);
-  for (int k = nl - 2; k >= 0; --k) {
-    c8_kry_level const& L = lv[k];
-    hipLaunchKernelGGL((k_level_prolong<ND, NRES>), dim3((L.n + TPB - 1) / TPB), dim3(TPB), 0, st, L.n, level_agg_tables(L), x_of(k + 1), x_of(k), q.S);
-    int const ncol = (int)L.color_ptr.size() - 1;
-    auto color = [&](int j) {
-      int const lo = L.color_ptr[j], m = L.color_ptr[j + 1] - lo, npb = TPB / LEVEL_G;
-      hipLaunchKernelGGL((k_level_sgs<NC>), dim3((m + npb - 1) / npb), dim3(TPB), 0, st, L.d_colors + lo, m, level_tables(L), L.d_minv, rhs_of(k), x_of(k), q.S);
-    };
-    for (int s = 0; s < c->kry_sweeps; ++s) {
-      for (int j = 0; j < ncol; ++j) color(j);
-      for (int j = ncol - 2; j >= 0; --j) color(j);
-    }
-  }
-  hipLaunchKernelGGL((k_prolong<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, q.nn, q.nb_node, agg_tables(c), x_of(0), x, q.S);
+  double* const r1 = nl == 1 ? c->d_kry_cvec : lv[0].d_vec;
+  double const* const e1 = nl == 1 ? c->d_kry_cvec + lda : lv[0].d_vec + (size_t)lv[0].n * NC;
+  hipLaunchKernelGGL((k_restrict<ND, NRES>), dim3((c->kry_nagg + wpb - 1) / wpb), dim3(TPB), 0, st, c->kry_nagg, agg_tables(c), q.nn, rhs, r1, q.S);
+  hipError_t const err = launch_level_cycle<ND, NRES>(c, lv, q.S);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((k_prolong<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, q.nn, q.nb_node, agg_tables(c), e1, x, q.S);
   return hipGetLastError();
 }

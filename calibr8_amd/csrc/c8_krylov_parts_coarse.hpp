@@ -69,7 +69,11 @@ __global__ void __launch_bounds__(TPB) k_flags_unpack(int nown, int nn, int nd, 
 // arrays).  Ownership and order of the sums are those of k_galerkin: a work item owns its tile columns and walks the
 // aggregate's nodes in ascending id and each node's graph row in column order.  The unit diagonal of a zero column of P is
 // the owner's.  Output: rows (base + I) * NC ... of the dense global matrix; every other row of this rank's copy stays zero.
-template <int ND, int NRES>
+// SPARSE (the multilevel kind over parts, c8_krylov_parts_multilevel.hpp): the tile goes to the block-sparse replicated A_1
+// instead, the NC x NC block of neighbour `slot` to graph entry nbr_ptr_global[base + I] + slot of level 1.  The rank's
+// aggregates are consecutive rows of that graph and T.nbr_ptr counts the same lists from the rank's first row, so the entry
+// is nbr_ptr_global[base] + T.nbr_ptr[I] + slot and Ac points at entry nbr_ptr_global[base]; the sums are the same.
+template <int ND, int NRES, bool SPARSE = false>
 __global__ void __launch_bounds__(TPB) k_galerkin_parts(AggTables T, int base, int32_t const* __restrict__ nodeptr,
                                                         int32_t const* __restrict__ nodeadj, Blocks A, double* __restrict__ Ac, int lda) {
   constexpr int NB = CoarseDims<ND, NRES>::NB, NC = CoarseDims<ND, NRES>::NC;
@@ -138,7 +142,8 @@ __global__ void __launch_bounds__(TPB) k_galerkin_parts(AggTables T, int base, i
   __syncthreads();
   for (int idx = threadIdx.x; idx < NC * W; idx += TPB) {
     int const r = idx / W, q = idx % W;
-    Ac[(size_t)((base + I) * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
+    if (SPARSE) Ac[((size_t)(b0 + q / NC) * NC + r) * NC + q % NC] = tile[idx];
+    else Ac[(size_t)((base + I) * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
   }
 }
 
@@ -271,7 +276,7 @@ int parts_agree(Parts& P, char const* who, double finding, F what) {
 // num_owned changed: one all-reduce of one slot per rank, every slot written by one rank).
 int parts_aggregates(c8_ctx* c, Parts& P) {
   if (c->kry_pc_host_for == P.nown) return C8_OK;
-  c->kry_pc_host_for = -1, c->kry_pc_for = -1;
+  c->kry_pc_host_for = -1, c->kry_pc_for = -1, c->kry_pl_for = -1;
   int const nown = P.nown;
   std::vector<int32_t> gp(nown + 1, 0), ga;
   for (int i = 0; i < nown; ++i) {
@@ -291,6 +296,7 @@ int parts_aggregates(c8_ctx* c, Parts& P) {
   }
   c->kry_pc_agg_of = std::move(H.agg);
   c->kry_pc_ptr = std::move(H.ptr), c->kry_pc_nodes = std::move(H.nodes), c->kry_pc_off = std::move(H.off);
+  c->kry_pc_x = std::move(H.centroid);
   c->kry_pc_nagg = H.nagg;
   c->kry_pc_base = base, c->kry_pc_total = total;
   c->kry_pc_host_for = nown;
@@ -319,7 +325,7 @@ int parts_coarse_build(c8_ctx* c, Parts& P, char const* who) {
   if (c->kry_pc_for == P.nown) return C8_OK;
   int const nn = c->mesh.nnodes, nown = P.nown, nd = c->ndims, nc = coarse_columns(c);
   int const base = (int)c->kry_pc_base, total = (int)c->kry_pc_total;
-  c->kry_pc_for = -1;
+  c->kry_pc_for = -1, c->kry_pl_for = -1;
   for (void* b : {(void*)c->d_kry_pc_agg, (void*)c->d_kry_pc_off, (void*)c->d_kry_pc_flags, (void*)c->d_kry_pc_imp}) P.hip(hipFree(b), "hipFree");
   c->d_kry_pc_agg = nullptr, c->d_kry_pc_off = nullptr, c->d_kry_pc_flags = nullptr, c->d_kry_pc_imp = nullptr;
   size_t const nu = (size_t)nn * nd;
@@ -369,6 +375,7 @@ int parts_coarse_build(c8_ctx* c, Parts& P, char const* who) {
         for (int32_t e = gp[H.nodes[k]]; e < gp[H.nodes[k] + 1]; ++e)
           H.slot[e] = (int32_t)(std::lower_bound(H.nbr.begin() + lo, H.nbr.end(), H.agg[ga[e]]) - (H.nbr.begin() + lo));
     }
+    c->kry_pc_nbr_ptr = H.nbr_ptr, c->kry_pc_nbr = H.nbr;  // (rows of the level-1 graph of the multilevel kind over parts)
     double* none = nullptr;  // (the offsets are on the device already, imported: upload_aggregates gets one placeholder entry)
     H.off.assign(1, 0.);
     P.note(upload_aggregates(H, &c->d_kry_pc_agg, c->kry_pc_at, &none));
@@ -392,6 +399,22 @@ int parts_coarse_prepare(c8_ctx* c, Parts& P, char const* who) {
   return parts_coarse_build(c, P, who);
 }
 
+// The constrained flags of the gathered matrix of P.q at every local node: the owned rows' by k_constrained_own, the copies'
+// imported from their owners.  One import.
+template <int ND, int NRES, int G>
+void parts_flags(Parts& P) {
+  Solve const& q = P.q;
+  c8_ctx* c = q.c;
+  int const nb_g = (P.nown + TPB / G - 1) / (TPB / G), nb_copy = (q.nn - P.nown + TPB - 1) / TPB;
+  double* const imp = c->d_kry_pc_imp;
+  double* const seg1 = NRES == 2 ? imp + (size_t)q.nn * ND : nullptr;
+  C8_PARTS_LAUNCH(P, (k_constrained_own<ND, NRES, G>), xcd_grid(nb_g), TPB, P.nown, nb_g, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_pc_flags);
+  C8_PARTS_LAUNCH(P, k_flags_pack, P.nb_own, TPB, P.nown, ND, c->d_kry_pc_flags, imp);
+  P.note(c8_halo_import_start(P.h, imp, seg1, P.failed));
+  P.note(c8_halo_import_finish(P.h, imp, seg1, P.failed));
+  C8_PARTS_LAUNCH(P, k_flags_unpack, nb_copy, TPB, P.nown, q.nn, ND, imp, c->d_kry_pc_flags);
+}
+
 // The coarse level for the gathered matrix of P.q, up to the all-reduced A_c (invert = false) or to its checked inverse.
 // Errors go to P; parts_coarse_agree() after it gives every rank the same code.
 template <int ND, int NRES, int G>
@@ -410,14 +433,7 @@ void parts_coarse_setup(Parts& P, bool invert) {
   if (!P.failed) P.hip(hipMemcpyAsync(info, h_info, sizeof(h_info), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (!P.failed) P.hip(hipMemsetAsync(c->d_kry_Ac, 0, (size_t)n * lda * sizeof(double), st), "hipMemsetAsync");
   if (!P.failed) P.hip(hipMemsetAsync(c->d_kry_cvec, 0, 2 * (size_t)lda * sizeof(double), st), "hipMemsetAsync");
-  int const nb_g = (P.nown + TPB / G - 1) / (TPB / G), nb_copy = (q.nn - P.nown + TPB - 1) / TPB;
-  double* const imp = c->d_kry_pc_imp;
-  double* const seg1 = NRES == 2 ? imp + (size_t)q.nn * ND : nullptr;
-  C8_PARTS_LAUNCH(P, (k_constrained_own<ND, NRES, G>), xcd_grid(nb_g), TPB, P.nown, nb_g, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_pc_flags);
-  C8_PARTS_LAUNCH(P, k_flags_pack, P.nb_own, TPB, P.nown, ND, c->d_kry_pc_flags, imp);
-  P.note(c8_halo_import_start(P.h, imp, seg1, P.failed));
-  P.note(c8_halo_import_finish(P.h, imp, seg1, P.failed));
-  C8_PARTS_LAUNCH(P, k_flags_unpack, nb_copy, TPB, P.nown, q.nn, ND, imp, c->d_kry_pc_flags);
+  parts_flags<ND, NRES, G>(P);
   if (!P.failed && nagg > 0) {
     hipLaunchKernelGGL((k_galerkin_parts<ND, NRES>), dim3(nagg), dim3(TPB), lds, st, parts_agg_tables(c), base, c->d_nodeptr, c->d_nodeadj, q.A,
                        c->d_kry_Ac, lda);
@@ -482,8 +498,15 @@ void parts_iteration_two_level(Parts& P) {
 }
 
 int build_colors(c8_ctx* c);
+// (c8_krylov_parts_multilevel.hpp, included after this file: the same four steps for C8_PRECOND_MULTILEVEL_PARTS)
+int parts_levels_prepare(c8_ctx* c, Parts& P, char const* who);
+template <int ND, int NRES, int G>
+void parts_levels_setup(Parts& P, int upto);
+int parts_levels_agree(Parts& P, char const* who);
+template <int ND, int NRES>
+void parts_levels_apply(Parts& P, double const* rhs, double* x);
 
-// c8_krylov_precondition with the kind over parts selected and a halo attached: y = M^-1 v on the owned entries.  COLLECTIVE:
+// c8_krylov_precondition with a kind over parts selected (two levels, or the multilevel one) and a halo attached: y = M^-1 v on the owned entries.  COLLECTIVE:
 // the set-up of the coarse level and the all-reduce of the apply; the refusals (a bad diagonal block, a vector or matrix that
 // is not finite, a singular A_c) are agreed over the ranks.
 template <int ND, int NRES, int G>
@@ -493,7 +516,8 @@ int precondition_parts(c8_ctx* c, const c8_system* sys, const double* const v[2]
   Parts P = parts_of(c);
   Solve& q = P.q;
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_precondition: empty mesh");
-  int rc = parts_coarse_prepare(c, P, who);
+  bool const multi = c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
+  int rc = multi ? parts_levels_prepare(c, P, who) : parts_coarse_prepare(c, P, who);
   if (rc != C8_OK) return rc;
   int const nown = P.nown;
   size_t const n0 = (size_t)q.nn * ND, nu = (size_t)nown * ND, np_ = NRES == 2 ? (size_t)nown : (size_t)0;
@@ -532,10 +556,12 @@ int precondition_parts(c8_ctx* c, const c8_system* sys, const double* const v[2]
     return fail(C8_ERR_ARG, "c8_krylov_precondition: the vector or the matrix is not finite on rank " + std::to_string(r));
   });
   if (rc != C8_OK) return rc;
-  parts_coarse_setup<ND, NRES, G>(P, true);
-  if ((rc = parts_coarse_agree(P, who)) != C8_OK) return rc;
+  if (multi) parts_levels_setup<ND, NRES, G>(P, -1);
+  else parts_coarse_setup<ND, NRES, G>(P, true);
+  if ((rc = multi ? parts_levels_agree(P, who) : parts_coarse_agree(P, who)) != C8_OK) return rc;
   C8_PARTS_LAUNCH(P, (k_vec<1>), P.nb_upd, TPB, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
-  parts_coarse<ND, NRES>(P, q.s, q.shat);
+  if (multi) parts_levels_apply<ND, NRES>(P, q.s, q.shat);
+  else parts_coarse<ND, NRES>(P, q.s, q.shat);
   if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, false), "k_sgs_color");
   if (!P.failed && nu > 0) P.hip(hipMemcpyAsync(y[0], q.shat, nu * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
   if (!P.failed && NRES == 2 && np_ > 0) P.hip(hipMemcpyAsync(y[1], q.shat + n0, np_ * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");

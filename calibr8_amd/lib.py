@@ -13,6 +13,7 @@ C8_SCALE_NONE, C8_SCALE_LOG, C8_SCALE_BOUNDS = 0, 1, 2
 C8_PRECOND_BLOCK_JACOBI, C8_PRECOND_BLOCK_SGS, C8_PRECOND_TWO_LEVEL = 0, 1, 3  # (2 is not a kind: refused)
 C8_PRECOND_MULTILEVEL = 5  # (nor is 4)
 C8_PRECOND_TWO_LEVEL_PARTS = 7  # (nor is 6): the two-level kind with a coarse space over the parts of a multi-part mesh
+C8_PRECOND_MULTILEVEL_PARTS = 9  # (nor is 8): the multilevel kind over parts, the levels from 1 down replicated on every rank
 
 dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)

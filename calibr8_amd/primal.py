@@ -95,7 +95,11 @@ def distributed_device_solver(asm, rel_tol=1e-10, max_iters=20000, preconditione
     for `device_solver`; "sgs" is part-local here (columns owned by other parts are dropped inside the sweeps); "two_level" and
     "multilevel" cover one part only and the library refuses them here; "two_level_parts" is the two-level kind over parts
     (C8_PRECOND_TWO_LEVEL_PARTS: aggregates per part, a dense coarse problem over all parts on every rank, capped at 8192
-    coarse unknowns in total; two more all-reduces per preconditioner apply)."""
+    coarse unknowns in total; two more all-reduces per preconditioner apply); "multilevel_parts" is the multilevel kind over
+    parts (C8_PRECOND_MULTILEVEL_PARTS: the same aggregates per part as level 0, then the block-sparse levels of "multilevel"
+    from level 1 down, replicated on every rank and set by Assembler.set_krylov_multilevel; the dense solve is that of the last
+    level only, so the cap of 8192 no longer binds the mesh; the same two all-reduces per apply, and one all-reduce of the
+    level-1 matrix per set-up)."""
     return DeviceSolver(asm, rel_tol=rel_tol, max_iters=max_iters, parts=True, preconditioner=preconditioner, sweeps=sweeps, **opts)
 
 

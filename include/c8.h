@@ -535,8 +535,51 @@ enum { C8_PRECOND_MULTILEVEL = 5 };
  * entries.  The first of these calls (or the first solve) after a halo is attached is collective too: it counts the
  * aggregates over the ranks.  With the other coarse kinds selected all of them keep refusing a halo. */
 enum { C8_PRECOND_TWO_LEVEL_PARTS = 7 };  /* 6 stays unassigned, as 2 and 4 */
+/* C8_PRECOND_MULTILEVEL_PARTS is the multilevel kind over the parts of a multi-part mesh: the distributed level 0 of
+ * C8_PRECOND_TWO_LEVEL_PARTS over the block-sparse levels of C8_PRECOND_MULTILEVEL, which are replicated on every rank from
+ * level 1 down.  It lifts the cap of 8192 coarse unknowns of the two-level kind over parts.  Without a halo it IS
+ * C8_PRECOND_MULTILEVEL (the same launches); c8_krylov_solve keeps refusing a halo.  With a halo attached
+ * (c8_krylov_solve_parts, c8_krylov_linear_solve_parts, c8_krylov_precondition; NC = 7, 4 or 3 as above):
+ *   level 0   that of C8_PRECOND_TWO_LEVEL_PARTS, unchanged: aggregates of the rank's owned sub-graph, global id = base_r +
+ *             local id, centroids summed in ascending local id, P_0 zero on constrained equations by the rule over the whole
+ *             owned row, ids, offsets and flags imported at the ghost and phantom copies.
+ *   level 1 graph   global, replicated on every rank.  Aggregates I and J of any ranks are neighbours when an owned node of I
+ *             has a graph column (owned, ghost or phantom) whose owner put it into J, self included; rows in ascending global
+ *             id.  Every rank knows the rows of its own aggregates; host all-reduces over the halo's communicator, in which
+ *             every entry is written by one rank and is zero elsewhere, carry the row lengths (one slot per global
+ *             aggregate), then the column ids, then the centroids (total x ND); ids travel as doubles.  The result is exact
+ *             and bitwise equal on every rank, for any number of parts.  Done once per attached halo, again when num_owned
+ *             changes and when c8_krylov_set_multilevel changes a setting (that call serves both multilevel kinds).
+ *   levels >= 2   from the replicated level 1 by the host rules of C8_PRECOND_MULTILEVEL (aggregates, colours, the
+ *             continuation rule: level 1 always exists; another level is built while n_l x NC > coarse_max, fewer than
+ *             max_levels levels exist, level 0 counting, and aggregation still reduces the node count).  The same host code on
+ *             the same bits gives every rank the same hierarchy without a message.  P_l for l >= 1, the constrained rule on
+ *             A_l, the unit diagonal of a zero column and the dense last level are those of C8_PRECOND_MULTILEVEL.  A last
+ *             level above 8192 unknowns: C8_ERR_UNSUPPORTED on every rank before anything is assembled or iterated, the
+ *             message names its size and what ended the recursion.
+ *   A_1       = P_0^T A P_0 over all parts, block-sparse over the level-1 graph, one row-major NC x NC block per graph entry,
+ *             replicated.  Rank r forms the block rows of its own aggregates, ghost and phantom columns with the imported
+ *             P_j; one all-reduce of the nnz_1 x NC^2 doubles follows (every entry is one value plus zeros: exact in any
+ *             order).  A_l, l >= 2, is then formed and set up on every rank.
+ *   y = M^-1 v   r_1 = P_0^T v in the rank's own slots and zeros elsewhere, one all-reduce of the n_1 doubles; every rank
+ *             runs the cycle of C8_PRECOND_MULTILEVEL on the whole level-1 vector (down the replicated levels, the dense
+ *             solve, up with `sweeps` coloured sweeps per block level, level 1 included); x = P_0 e on the owned nodes; then
+ *             `sweeps` part-local sweeps on level 0 started from this x.  A fixed linear operator; an iteration of the solve
+ *             makes two imports and five all-reduces, as with C8_PRECOND_TWO_LEVEL_PARTS.  When level 1 is the last level
+ *             (n_1 x NC <= coarse_max, or max_levels = 2) the launches are those of C8_PRECOND_TWO_LEVEL_PARTS and the results
+ *             have its bytes.
+ * A singular or non-finite diagonal block on any level, a singular last level, a device error on a rank and an aggregate with
+ * too many neighbours for a kernel's tile are agreed over the ranks: every rank returns the same code; a bad node block of
+ * level 0 names node and rank.  With this kind selected and a halo attached: c8_krylov_aggregates, c8_krylov_aggregate_base
+ * and c8_krylov_coarse_matrix (cap included) behave as with C8_PRECOND_TWO_LEVEL_PARTS; c8_krylov_levels gives the level
+ * count, level 0 included; c8_krylov_level(0) the rank's own view (num_owned nodes, local aggregate ids, the part-local
+ * colour lists), c8_krylov_level(l >= 1) the replicated level; c8_krylov_level_matrix(l >= 1) is COLLECTIVE and downloads the
+ * dense global A_l on every rank; c8_krylov_precondition is COLLECTIVE and applies the operator to the owned entries.  The
+ * first of these calls after a halo is attached or a setting changed is collective too.  C8_PRECOND_TWO_LEVEL and
+ * C8_PRECOND_MULTILEVEL keep refusing a halo. */
+enum { C8_PRECOND_MULTILEVEL_PARTS = 9 };  /* 8 stays unassigned, as 2, 4 and 6 */
 int c8_krylov_set_preconditioner(c8_ctx* ctx, int kind, int sweeps);
-/* The two settings of C8_PRECOND_MULTILEVEL (<= 0: the default): coarse_max, default 1024 unknowns, and max_levels, default
+/* The two settings of C8_PRECOND_MULTILEVEL and C8_PRECOND_MULTILEVEL_PARTS (<= 0: the default): coarse_max, default 1024 unknowns, and max_levels, default
  * 8, at least 2.  The levels are rebuilt at the next use.  C8_ERR_ARG for a null context, for max_levels = 1, and while a
  * staged assembly waits for c8_gather_finish. */
 int c8_krylov_set_multilevel(c8_ctx* ctx, int32_t coarse_max, int32_t max_levels);
