@@ -13,7 +13,8 @@
 
 int c8_fail(int code, std::string const& msg);  // records c8_last_error() and returns code
 
-// a level l >= 1 of the multilevel preconditioner (c8_krylov_multilevel.hpp): one node per aggregate of the level above
+// a level l >= 1 of an aggregation preconditioner (c8_krylov_multilevel.hpp): one node per aggregate of the level above.
+// Over parts only n is set in the one-level list of the two-level kind (the dense last level needs no more).
 struct c8_kry_level {
   int n = 0;                          // nodes
   std::vector<int32_t> gp, ga;        // graph: the neighbour lists of the aggregates it came from (sorted, self included)
@@ -133,7 +134,8 @@ struct c8_ctx {
   std::vector<int32_t> kry_color_ptr, kry_color_nodes;
   int kry_colors_for = -2;           // what the colour lists were built for: -1 no halo, else num_owned (-2: not built)
   int32_t* d_kry_colors = nullptr;   // device mirror of kry_color_nodes
-  // ... the coarse level of C8_PRECOND_TWO_LEVEL (c8_krylov_coarse.hpp): aggregates of the node graph, built at first use
+  // ... level 0 of C8_PRECOND_TWO_LEVEL and C8_PRECOND_MULTILEVEL (c8_krylov_coarse.hpp): aggregates of the node graph, built
+  // at first use, and the dense last level of every aggregation kind
   int kry_nagg = -1;                 // number of aggregates (-1: not built)
   int kry_agg_max_nbr = 0;           // most neighbouring aggregates of one aggregate (itself included)
   std::vector<int32_t> kry_agg_of;   // [nnodes] aggregate of a node (c8_krylov_aggregates)
@@ -143,20 +145,23 @@ struct c8_ctx {
   int32_t* d_kry_cflags = nullptr;   // [nnodes] constrained-row flags of the current matrix
   double* d_kry_Ac = nullptr;        // A_c, then its inverse: dense, row-major, even leading dimension
   double* d_kry_cvec = nullptr;      // r_c and e
-  int32_t* d_kry_ipiv = nullptr;     // pivots of the LU factorisation, then the three status words of the set-up
+  int32_t* d_kry_ipiv = nullptr;     // pivots of the LU factorisation, then the status words of the set-up (3 + one per level)
   size_t kry_Ac_n = 0, kry_cvec_n = 0, kry_ipiv_n = 0;
   void* kry_rocblas = nullptr;       // rocblas_handle of the dense inverse (workspace inside), made at first use
+  std::vector<c8_kry_level> kry_agg_levels;           // the list of C8_PRECOND_TWO_LEVEL: level 1 alone (n, graph = the neighbour
+                                                      // lists of the aggregates, positions = their centroids); no device buffers
   // ... the levels of C8_PRECOND_MULTILEVEL below level 0 (c8_krylov_multilevel.hpp), built at first use and again after
-  // c8_krylov_set_multilevel; level 1's graph and positions come with the aggregates above
-  std::vector<int32_t> kry_agg_nbr_ptr, kry_agg_nbr;  // neighbouring aggregates of every aggregate: the graph of level 1
-  std::vector<double> kry_agg_x;     // [kry_nagg][3] centroids
+  // c8_krylov_set_multilevel: a copy of kry_agg_levels extended downwards, a list of its own so that switching between
+  // the kinds rebuilds neither
   int kry_ml_coarse_max = 0, kry_ml_max_levels = 0;   // (set by c8_krylov.hip: <= 0 until the first use = the defaults)
   bool kry_ml_built = false;
   std::vector<c8_kry_level> kry_levels;               // [k] is level k + 1; freed by c8_krylov_release
-  // ... the coarse level of C8_PRECOND_TWO_LEVEL_PARTS (c8_krylov_parts_coarse.hpp): aggregates of the owned sub-graph
+  // ... level 0 of C8_PRECOND_TWO_LEVEL_PARTS and C8_PRECOND_MULTILEVEL_PARTS (c8_krylov_parts_levels.hpp): aggregates of
+  // the owned sub-graph
   int kry_pc_host_for = -1;          // num_owned the host lists and the counts were built for (-1: not built)
   int kry_pc_for = -1;               // num_owned the device tables were built for (-1: not built; reset by c8_halo_attach)
-  int kry_pc_nagg = 0, kry_pc_max_nbr = 0, kry_pc_bad = -1;  // this rank's aggregates; widest block row; bad row of the last set-up
+  int kry_pc_nagg = 0, kry_pc_max_nbr = 0;                   // this rank's aggregates; widest block row
+  double kry_pc_bad = -1.;           // finding of the last set-up of either kind: level * 2^32 + block or row (-1: none)
   long long kry_pc_base = 0, kry_pc_total = 0;               // aggregates of the ranks below this one, of all ranks
   std::vector<int32_t> kry_pc_agg_of, kry_pc_ptr, kry_pc_nodes;  // [num_owned] LOCAL aggregate ids; node lists of the aggregates
   std::vector<double> kry_pc_off;    // [num_owned][ndims] node - centroid
@@ -165,13 +170,13 @@ struct c8_ctx {
   double* d_kry_pc_off = nullptr;    // [nnodes][ndims], the copies' entries imported from their owners
   int32_t* d_kry_pc_flags = nullptr; // [nnodes] constrained-row flags of the current matrix, the copies' imported
   double* d_kry_pc_imp = nullptr;    // a vector's worth of doubles: what the import tables move the ids and the flags in
-  // ... the levels of C8_PRECOND_MULTILEVEL_PARTS below level 0 (c8_krylov_parts_multilevel.hpp): level 1 is the graph of
+  std::vector<c8_kry_level> kry_pc_levels;            // the list of C8_PRECOND_TWO_LEVEL_PARTS: level 1 alone, n = kry_pc_total
+  // ... the levels of C8_PRECOND_MULTILEVEL_PARTS below level 0: level 1 is the graph of
   // the aggregates of all ranks, replicated on every rank from the lists below; a list of its own, so that switching
   // between the kinds rebuilds neither
   std::vector<int32_t> kry_pc_nbr_ptr, kry_pc_nbr;  // neighbouring aggregates (GLOBAL ids, ascending) of this rank's aggregates
   std::vector<double> kry_pc_x;      // [kry_pc_nagg][3] centroids of this rank's aggregates
   int kry_pl_for = -1;               // num_owned the levels were built for (-1: not built; reset by c8_halo_attach and c8_krylov_set_multilevel)
-  double kry_pl_bad = -1.;           // finding of the last set-up: level * 2^32 + block or row (-1: none)
   std::vector<c8_kry_level> kry_pl_levels;            // [k] is level k + 1; freed by c8_krylov_release
 };
 void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree

@@ -17,15 +17,17 @@
 //
 // With c8_krylov_set_preconditioner(C8_PRECOND_BLOCK_SGS) the two k_prec launches become k_vec (the vector update alone,
 // out = 0) followed by the multicolour Gauss-Seidel sweeps of k_sgs_color, one launch per colour;
-// every other launch of the iteration is the same.  With C8_PRECOND_TWO_LEVEL the sweeps start from the coarse correction
-// x = P A_c^-1 P^T rhs instead of 0 (k_restrict, k_coarse_apply, k_prolong after k_vec; c8_krylov_coarse.hpp, DESIGN.md
-// section 13d), and the set-up of a solve forms A_c and its dense inverse.
-// C8_PRECOND_TWO_LEVEL_PARTS is that kind without a halo; over parts it is the coarse space of c8_krylov_parts_coarse.hpp
-// (DESIGN.md section 13f): part-local aggregates, a dense global A_c replicated on every rank, two more all-reduces per apply.
-// With C8_PRECOND_MULTILEVEL the coarse correction is itself a recursion over further aggregated levels (c8_krylov_multilevel.hpp,
-// DESIGN.md section 13e): block-sparse coarse matrices with sweeps of their own, the dense inverse on the last level only.
-// C8_PRECOND_MULTILEVEL_PARTS is that kind without a halo; over parts it keeps the distributed level 0 of the two-level kind
-// over parts and runs the levels from 1 down replicated on every rank (c8_krylov_parts_multilevel.hpp).
+// every other launch of the iteration is the same.  With the four aggregation kinds the sweeps start from a coarse
+// correction x = P_0 M_1^-1 P_0^T rhs instead of 0, over a list of aggregated levels of which the last is solved densely
+// (DESIGN.md sections 13d to 13h); the set-up of a solve forms every level's matrix and the dense inverse.  One code path
+// per error discipline serves them:
+//   c8_krylov_coarse.hpp        aggregation, P, the kernels between level 0 and level 1, the dense last level
+//   c8_krylov_multilevel.hpp    the block levels and the cycle; levels_setup / levels_apply of one part.
+//                               C8_PRECOND_TWO_LEVEL is a list of one level (k_restrict, k_coarse_apply, k_prolong),
+//                               C8_PRECOND_MULTILEVEL a list built by further aggregation
+//   c8_krylov_parts_levels.hpp  parts_levels_setup / parts_levels_apply over parts: part-local aggregates, level 1 and below
+//                               replicated on every rank, two more all-reduces per apply.  C8_PRECOND_TWO_LEVEL_PARTS and
+//                               C8_PRECOND_MULTILEVEL_PARTS; without a halo they are the kinds of one part
 //
 // Over the parts of a multi-part mesh (c8_krylov_solve_parts, second half of this file) the iteration is the same up to
 // the order of the sums.  Vectors keep the layout above with nnodes = the part's LOCAL count, so that ghost and phantom
@@ -467,6 +469,8 @@ int grow(T** buf, size_t* have, size_t need) {
   return C8_OK;
 }
 
+#include "c8_krylov_coarse.hpp"
+
 struct Solve {
   c8_ctx* c;
   int nn, nb_node, nb_spmv, nb_upd;
@@ -476,9 +480,11 @@ struct Solve {
   double *x, *r, *rhat, *p, *v, *s, *t, *phat, *shat, *part, *minv;
   KryScalars* S;
   double tol2 = 0.;
+  // the aggregation kinds: the levels below level 0 ([k] is level k + 1), the wording of the kind, level 0
+  std::vector<c8_kry_level> const* lv = nullptr;
+  bool multi = false;
+  Level0 l0{};
 };
-
-#include "c8_krylov_coarse.hpp"
 
 template <int ND, int NRES>
 int launch_setup(Solve const& q) {
@@ -527,7 +533,7 @@ int launch_iteration(Solve const& q) {
 // x = M^-1 rhs by the context's number of symmetric sweeps, x = 0 on entry (k_vec): colours 0 .. nc - 1, then nc - 2 .. 0,
 // one launch each.  Every launch is the general form -- the first forward sweep reads the zeros of the colours it has not
 // reached yet -- except colour 0 of the first sweep, which reads no column at all (colbound 0: x_i = D_i^-1 rhs_i).
-// from_zero = false (the two-level kind: x holds the coarse correction on entry) gives that launch the full bound too.
+// from_zero = false (the aggregation kinds: x holds the coarse correction on entry) gives that launch the full bound too.
 template <int ND, int NRES, int G>
 hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x, bool from_zero = true) {
   c8_ctx const* c = q.c;
@@ -549,15 +555,28 @@ hipError_t launch_sgs(Solve const& q, int colbound, double const* rhs, double* x
   return hipSuccess;
 }
 
-// launch_iteration with the Gauss-Seidel sweeps in the place of the D^-1 multiplication
-template <int ND, int NRES, int G>
+void color_graph(int n, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, std::vector<int32_t>* color_ptr,
+                 std::vector<int32_t>* color_nodes);
+#include "c8_krylov_multilevel.hpp"
+
+// The levels of q and its level 0 for a kind of one part, after the kind's refusals (coarse_refusals, multilevel_refusals)
+void use_levels(Solve& q, bool multi) {
+  q.lv = multi ? &q.c->kry_levels : &q.c->kry_agg_levels;
+  q.multi = multi;
+  q.l0 = level0(q.c);
+}
+
+// launch_iteration with the Gauss-Seidel sweeps in the place of the D^-1 multiplication; COARSE (the aggregation kinds):
+// the sweeps start from the coarse correction of their right-hand side
+template <int ND, int NRES, int G, bool COARSE>
 int launch_iteration_sgs(Solve const& q) {
   hipStream_t const st = q.c->stream;
   int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
   size_t const n0 = (size_t)q.nn * ND;
   hipLaunchKernelGGL((k_vec<0>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.p, q.phat, q.S);
   C8_HIP(hipGetLastError());
-  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat)));
+  if (COARSE) C8_HIP((levels_apply<ND, NRES>(q, q.p, q.phat)));
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat, !COARSE)));
   hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
                      q.part, q.S);
   C8_HIP(hipGetLastError());
@@ -565,7 +584,8 @@ int launch_iteration_sgs(Solve const& q) {
   C8_HIP(hipGetLastError());
   hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.s, q.shat, q.S);
   C8_HIP(hipGetLastError());
-  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat)));
+  if (COARSE) C8_HIP((levels_apply<ND, NRES>(q, q.s, q.shat)));
+  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat, !COARSE)));
   hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
                      q.part, q.S);
   C8_HIP(hipGetLastError());
@@ -578,57 +598,33 @@ int launch_iteration_sgs(Solve const& q) {
   return C8_OK;
 }
 
-void color_graph(int n, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, std::vector<int32_t>* color_ptr,
-                 std::vector<int32_t>* color_nodes);
-#include "c8_krylov_multilevel.hpp"
-
-// launch_iteration_sgs with the sweeps started from the coarse correction of their right-hand side: of the two-level kind,
-// or of the multilevel one (MULTI)
-template <int ND, int NRES, int G, bool MULTI = false>
-int launch_iteration_two_level(Solve const& q) {
-  hipStream_t const st = q.c->stream;
-  int32_t const *np = q.c->d_nodeptr, *na = q.c->d_nodeadj;
-  size_t const n0 = (size_t)q.nn * ND;
-  hipLaunchKernelGGL((k_vec<0>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.p, q.phat, q.S);
-  C8_HIP(hipGetLastError());
-  C8_HIP((MULTI ? launch_multilevel<ND, NRES>(q, q.p, q.phat) : launch_coarse<ND, NRES>(q, q.p, q.phat)));
-  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.p, q.phat, false)));
-  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 0>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.phat, q.v, q.rhat,
-                     q.part, q.S);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_reduce<0>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, q.n, (size_t)0, n0, q.r, q.v, q.s, q.shat, q.S);
-  C8_HIP(hipGetLastError());
-  C8_HIP((MULTI ? launch_multilevel<ND, NRES>(q, q.s, q.shat) : launch_coarse<ND, NRES>(q, q.s, q.shat)));
-  C8_HIP((launch_sgs<ND, NRES, G>(q, q.nn, q.s, q.shat, false)));
-  hipLaunchKernelGGL((k_spmv<ND, NRES, G, 1>), dim3(xcd_grid(q.nb_spmv)), dim3(TPB), 0, st, q.nn, q.nb_spmv, np, na, q.A, q.shat, q.t, q.s,
-                     q.part, q.S);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_reduce<1>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_spmv, 0., q.S);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_update, dim3(q.nb_upd), dim3(TPB), 0, st, q.n, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_reduce<2>), dim3(1), dim3(TPB), 0, st, q.part, q.nb_upd, q.tol2, q.S);
-  C8_HIP(hipGetLastError());
-  return C8_OK;
+inline bool aggregation_kind(int kind) {
+  return kind == C8_PRECOND_TWO_LEVEL || kind == C8_PRECOND_MULTILEVEL || kind == C8_PRECOND_TWO_LEVEL_PARTS || kind == C8_PRECOND_MULTILEVEL_PARTS;
 }
+inline bool multilevel_kind(int kind) { return kind == C8_PRECOND_MULTILEVEL || kind == C8_PRECOND_MULTILEVEL_PARTS; }
 
 struct Launchers {
   int (*setup)(Solve const&);
   int (*residual)(Solve const&);
   int (*iteration)(Solve const&);
-  int (*coarse)(Solve const&, bool);  // the coarse level of the two-level kind (coarse_setup)
-  int (*levels)(Solve const&, int);   // the hierarchy of the multilevel kind (multilevel_setup)
+  int (*levels)(Solve const&, int);  // the levels of an aggregation kind for the matrix (levels_setup)
   int group;
 };
 template <int ND, int NRES, int G>
 Launchers launchers(int kind) {
   return Launchers{launch_setup<ND, NRES>, launch_residual<ND, NRES>,
-                   (kind == C8_PRECOND_MULTILEVEL || kind == C8_PRECOND_MULTILEVEL_PARTS) ? launch_iteration_two_level<ND, NRES, G, true>
-                   : (kind == C8_PRECOND_TWO_LEVEL || kind == C8_PRECOND_TWO_LEVEL_PARTS) ? launch_iteration_two_level<ND, NRES, G>
-                   : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G> : launch_iteration<ND, NRES, G>,
-                   coarse_setup<ND, NRES, G>, multilevel_setup<ND, NRES, G>, G};
+                   aggregation_kind(kind) ? launch_iteration_sgs<ND, NRES, G, true>
+                   : kind == C8_PRECOND_BLOCK_SGS ? launch_iteration_sgs<ND, NRES, G, false> : launch_iteration<ND, NRES, G>,
+                   levels_setup<ND, NRES, G>, G};
+}
+// the one dispatch over (ndims, nres) of the solve of one part (false: no kernels)
+bool launchers_of(c8_ctx const* c, Launchers* L) {
+  bool const two = c->nres == 2;
+  if (c->ndims == 3 && two) *L = launchers<3, 2, 16>(c->kry_precond);
+  else if (c->ndims == 2 && two) *L = launchers<2, 2, 8>(c->kry_precond);
+  else if (c->ndims == 2 && !two) *L = launchers<2, 1, 8>(c->kry_precond);
+  else return false;
+  return true;
 }
 
 int read_scalars(Solve const& q, KryScalars* h) {
@@ -936,41 +932,74 @@ void parts_iteration(Parts& P) {
   parts_scalars<2>(P, P.nb_upd);
 }
 
-// parts_iteration with the part-local Gauss-Seidel sweeps (columns < num_owned) in the place of the D^-1 multiplication
-template <int ND, int NRES, int G>
+#include "c8_krylov_parts_levels.hpp"
+
+// parts_iteration with the part-local Gauss-Seidel sweeps (columns < num_owned) in the place of the D^-1 multiplication;
+// COARSE (the aggregation kinds over parts): the sweeps start from the coarse correction of their right-hand side, which
+// makes two imports and five all-reduces per iteration
+template <int ND, int NRES, int G, bool COARSE>
 void parts_iteration_sgs(Parts& P) {
   Solve const& q = P.q;
   size_t const n0 = (size_t)q.nn * ND, nu = (size_t)P.nown * ND, np_ = NRES == 2 ? (size_t)P.nown : (size_t)0;
   C8_PARTS_LAUNCH(P, (k_vec<0>), P.nb_upd, TPB, nu, np_, n0, q.r, q.v, q.p, q.phat, q.S);
-  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.p, q.phat), "k_sgs_color");
+  if (COARSE) parts_levels_apply<ND, NRES>(P, q.p, q.phat);
+  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.p, q.phat, !COARSE), "k_sgs_color");
   parts_spmv<ND, NRES, G, 0>(P, q.phat, P.phat1, q.v, q.rhat);
   parts_scalars<0>(P, P.nb_int + P.nb_bnd);
   C8_PARTS_LAUNCH(P, (k_vec<1>), P.nb_upd, TPB, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
-  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.s, q.shat), "k_sgs_color");
+  if (COARSE) parts_levels_apply<ND, NRES>(P, q.s, q.shat);
+  if (!P.failed) P.hip(launch_sgs<ND, NRES, G>(q, P.nown, q.s, q.shat, !COARSE), "k_sgs_color");
   parts_spmv<ND, NRES, G, 1>(P, q.shat, P.shat1, q.t, q.s);
   parts_scalars<1>(P, P.nb_int + P.nb_bnd);
   C8_PARTS_LAUNCH(P, k_update_own, P.nb_upd, TPB, nu, np_, n0, q.x, q.r, q.s, q.t, q.phat, q.shat, q.rhat, q.part, q.S);
   parts_scalars<2>(P, P.nb_upd);
 }
 
-#include "c8_krylov_parts_coarse.hpp"
-#include "c8_krylov_parts_multilevel.hpp"
-
 struct PartsLaunchers {
   void (*setup)(Parts&);
   void (*residual)(Parts&);
   void (*iteration)(Parts&);
-  void (*coarse)(Parts&, bool);  // the coarse level of the two-level kind over parts (parts_coarse_setup)
-  void (*levels)(Parts&, int);   // the hierarchy of the multilevel kind over parts (parts_levels_setup)
+  void (*levels)(Parts&, int);  // the levels of an aggregation kind over parts for the matrix (parts_levels_setup)
   int group;
 };
 template <int ND, int NRES, int G>
 PartsLaunchers parts_launchers(int kind) {
   return PartsLaunchers{parts_setup<ND, NRES>, parts_residual<ND, NRES>,
-                        kind == C8_PRECOND_MULTILEVEL_PARTS ? parts_iteration_multilevel<ND, NRES, G>
-                        : kind == C8_PRECOND_TWO_LEVEL_PARTS ? parts_iteration_two_level<ND, NRES, G>
-                        : kind == C8_PRECOND_BLOCK_SGS ? parts_iteration_sgs<ND, NRES, G> : parts_iteration<ND, NRES, G>,
-                        parts_coarse_setup<ND, NRES, G>, parts_levels_setup<ND, NRES, G>, G};
+                        (kind == C8_PRECOND_MULTILEVEL_PARTS || kind == C8_PRECOND_TWO_LEVEL_PARTS) ? parts_iteration_sgs<ND, NRES, G, true>
+                        : kind == C8_PRECOND_BLOCK_SGS ? parts_iteration_sgs<ND, NRES, G, false> : parts_iteration<ND, NRES, G>,
+                        parts_levels_setup<ND, NRES, G>, G};
+}
+// the one dispatch over (ndims, nres) of the solve over parts (false: no kernels)
+bool parts_launchers_of(c8_ctx const* c, PartsLaunchers* L) {
+  bool const two = c->nres == 2;
+  if (c->ndims == 3 && two) *L = parts_launchers<3, 2, 16>(c->kry_precond);
+  else if (c->ndims == 2 && two) *L = parts_launchers<2, 2, 8>(c->kry_precond);
+  else if (c->ndims == 2 && !two) *L = parts_launchers<2, 1, 8>(c->kry_precond);
+  else return false;
+  return true;
+}
+
+// The dense copy of A_level of a list over parts on every rank: the code behind c8_krylov_level_matrix (multi: the levels
+// of C8_PRECOND_MULTILEVEL_PARTS) and c8_krylov_coarse_matrix (the two-level list, level 1) with a halo attached.
+// COLLECTIVE; without out_host the two-level list asks for its size alone and builds no tables.
+int parts_level_matrix(c8_ctx* c, const c8_system* sys, bool multi, int32_t level, int32_t* n_level, double* out_host, char const* who) {
+  Parts P = parts_of(c);
+  int rc = (multi || out_host) ? parts_levels_prepare(c, P, who, multi) : parts_coarse_refusals(c, P, who);
+  if (rc != C8_OK) return rc;
+  std::vector<c8_kry_level> const& lv = multi ? c->kry_pl_levels : c->kry_pc_levels;
+  int const nc = coarse_columns(c);
+  if (multi && (rc = level_matrix_refusals(lv, level, nc)) != C8_OK) return rc;
+  *n_level = lv[level - 1].n * nc;
+  if (!out_host) return C8_OK;
+  PartsLaunchers L;
+  if (!parts_launchers_of(c, &L)) return fail(C8_ERR_UNSUPPORTED, std::string(who) + ": no kernels for this number of dimensions and residuals");
+  P.q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  L.levels(P, level);
+  std::vector<double> blocks;
+  if (!P.failed) P.hip(level_copy_start(c, lv, level, nc, out_host, &blocks), "hipMemcpyAsync");
+  if (!P.failed) P.hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+  if (!P.failed) level_copy_finish(lv, level, nc, out_host, blocks);
+  return parts_agree(P, who, -1., [&](int, long long) { return C8_OK; });
 }
 
 // The host read of the scalars, COLLECTIVE: the ranks all-reduce (iterations, stop flag, their squares, failure marker).
@@ -1069,21 +1098,17 @@ int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], doub
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
   if ((c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) && c->halo)
     return precondition_parts<ND, NRES, G>(c, sys, v, y);  // (collective)
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
-  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
+  bool const coarse = aggregation_kind(c->kry_precond), multilevel = multilevel_kind(c->kry_precond);
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse;
   Solve q{};
   q.c = c;
   q.nn = c->mesh.nnodes;
   int const nown = c->halo ? c8_halo_num_owned(c->halo) : q.nn;
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_precondition: empty mesh");
-  if (two_level) {
-    int const rcc = coarse_refusals(c, "c8_krylov_precondition");
+  if (coarse) {
+    int const rcc = multilevel ? multilevel_refusals(c, "c8_krylov_precondition") : coarse_refusals(c, "c8_krylov_precondition");
     if (rcc != C8_OK) return rcc;
-  }
-  if (multilevel) {
-    int const rcc = multilevel_refusals(c, "c8_krylov_precondition");
-    if (rcc != C8_OK) return rcc;
+    use_levels(q, multilevel);
   }
   if (nown <= 0) return C8_OK;
   size_t const n0 = (size_t)q.nn * ND, nu = (size_t)nown * ND, np_ = NRES == 2 ? (size_t)nown : (size_t)0;
@@ -1120,14 +1145,12 @@ int precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], doub
     return fail(C8_ERR_ARG, "c8_krylov_precondition: the diagonal block of node " + std::to_string(h.bad_node) +
                             " is singular or not finite (node-block Jacobi preconditioner)");
   if (!std::isfinite(h.rr)) return fail(C8_ERR_ARG, "c8_krylov_precondition: the vector or the matrix is not finite");
-  if (two_level && (rc = coarse_setup<ND, NRES, G>(q, true)) != C8_OK) return rc;
-  if (multilevel && (rc = multilevel_setup<ND, NRES, G>(q, -1)) != C8_OK) return rc;
+  if (coarse && (rc = levels_setup<ND, NRES, G>(q, -1)) != C8_OK) return rc;
   if (sgs) {
     hipLaunchKernelGGL((k_vec<1>), dim3(q.nb_upd), dim3(TPB), 0, st, nu, np_, n0, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
-    if (two_level) C8_HIP((launch_coarse<ND, NRES>(q, q.s, q.shat)));
-    if (multilevel) C8_HIP((launch_multilevel<ND, NRES>(q, q.s, q.shat)));
-    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, !two_level && !multilevel)));
+    if (coarse) C8_HIP((levels_apply<ND, NRES>(q, q.s, q.shat)));
+    C8_HIP((launch_sgs<ND, NRES, G>(q, nown, q.s, q.shat, !coarse)));
   } else {
     hipLaunchKernelGGL((k_prec_own<ND, NRES, 1>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, nown, q.nn, q.nb_node, q.minv, q.r, q.v, q.s, q.shat, q.S);
     C8_HIP(hipGetLastError());
@@ -1165,14 +1188,10 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   double const abs_tol = (opts && opts->abs_tol > 0.) ? opts->abs_tol : 0.;
 
   // (no halo here: a kind over parts is the kind of one part)
-  bool const two_level = c->kry_precond == C8_PRECOND_TWO_LEVEL || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
-  bool const multilevel = c->kry_precond == C8_PRECOND_MULTILEVEL || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || two_level || multilevel;
+  bool const coarse = aggregation_kind(c->kry_precond), multilevel = multilevel_kind(c->kry_precond);
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse;
   Launchers L;
-  if (c->ndims == 3 && two) L = launchers<3, 2, 16>(c->kry_precond);
-  else if (c->ndims == 2 && two) L = launchers<2, 2, 8>(c->kry_precond);
-  else if (c->ndims == 2 && !two) L = launchers<2, 1, 8>(c->kry_precond);
-  else {
+  if (!launchers_of(c, &L)) {
     if (info) info->status = C8_ERR_UNSUPPORTED;
     return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve: no kernels for this number of dimensions and residuals");
   }
@@ -1188,14 +1207,11 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   q.nb_upd = (int)std::min<size_t>((q.n + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
   if (q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_solve: empty mesh");
   int rc;
-  if (two_level && (rc = coarse_refusals(c, "c8_krylov_solve")) != C8_OK) {
+  if (coarse && (rc = multilevel ? multilevel_refusals(c, "c8_krylov_solve") : coarse_refusals(c, "c8_krylov_solve")) != C8_OK) {
     if (info) info->status = rc;
     return rc;
   }
-  if (multilevel && (rc = multilevel_refusals(c, "c8_krylov_solve")) != C8_OK) {
-    if (info) info->status = rc;
-    return rc;
-  }
+  if (coarse) use_levels(q, multilevel);
   if (sgs && (rc = build_colors(c)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_minv, &c->kry_minv_n, (size_t)q.nn * nb * nb)) != C8_OK) return rc;
   if ((rc = grow(&c->d_kry_vec, &c->kry_vec_n, 9 * q.n)) != C8_OK) return rc;
@@ -1235,8 +1251,7 @@ static int solve(c8_ctx* c, const c8_system* sys, double* const dx[2], const c8_
   }
   double const tol = std::max(rel_tol * b_norm, abs_tol);
   q.tol2 = tol * tol;
-  if (two_level && (rc = L.coarse(q, true)) != C8_OK) return rc;  // A_c = P^T A P and its inverse for this matrix
-  if (multilevel && (rc = L.levels(q, -1)) != C8_OK) return rc;   // every A_l and the inverse of the last one
+  if (coarse && (rc = L.levels(q, -1)) != C8_OK) return rc;  // every A_l = P^T A P and the inverse of the last one for this matrix
 
   int restarts = 0, status = C8_NOT_CONVERGED;
   double true_norm = b_norm;
@@ -1296,13 +1311,10 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
 
   if (c->kry_precond == C8_PRECOND_TWO_LEVEL) return coarse_refusals(c, "c8_krylov_solve_parts");  // (a halo is attached: refused)
   if (c->kry_precond == C8_PRECOND_MULTILEVEL) return multilevel_refusals(c, "c8_krylov_solve_parts");
-  bool const coarse = c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS, multi = c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS;
-  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse || multi;
+  bool const multi = c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS, coarse = multi || c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS;
+  bool const sgs = c->kry_precond == C8_PRECOND_BLOCK_SGS || coarse;
   PartsLaunchers L;
-  if (c->ndims == 3 && two) L = parts_launchers<3, 2, 16>(c->kry_precond);
-  else if (c->ndims == 2 && two) L = parts_launchers<2, 2, 8>(c->kry_precond);
-  else if (c->ndims == 2 && !two) L = parts_launchers<2, 1, 8>(c->kry_precond);
-  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve_parts: no kernels for this number of dimensions and residuals");
+  if (!parts_launchers_of(c, &L)) return fail(C8_ERR_UNSUPPORTED, "c8_krylov_solve_parts: no kernels for this number of dimensions and residuals");
   int const nb = c->ndims + (two ? 1 : 0);
 
   Parts P;
@@ -1319,11 +1331,9 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   size_t const n0 = (size_t)q.nn * c->ndims;
   q.n = n0 + (two ? (size_t)q.nn : 0);
   int rc;
-  // the two-level kind over parts: the cap on the global coarse size and the tables of the coarse level, before anything
-  // is assembled or iterated (collective at the first use; every rank returns the same code)
-  if (coarse && (rc = parts_coarse_prepare(c, P, "c8_krylov_solve_parts")) != C8_OK) return rc;
-  // the multilevel kind over parts: the replicated levels and the cap on the last of them, in the same place
-  if (multi && (rc = parts_levels_prepare(c, P, "c8_krylov_solve_parts")) != C8_OK) return rc;
+  // the aggregation kinds over parts: the tables of level 0, the replicated levels and the cap on the dense last level,
+  // before anything is assembled or iterated (collective at the first use; every rank returns the same code)
+  if (coarse && (rc = parts_levels_prepare(c, P, "c8_krylov_solve_parts", multi)) != C8_OK) return rc;
   // from here on every rank goes through the same sequence of collectives, whatever happens to it
   P.note(build_part_lists(c));
   if (sgs) P.note(build_colors(c));
@@ -1384,11 +1394,7 @@ static int solve_parts(c8_ctx* c, const c8_system* sys, double* const dx[2], con
   }
   double const tol = std::max(rel_tol * b_norm, abs_tol);
   q.tol2 = tol * tol;
-  if (coarse) {  // A_c = P^T A P over all parts and its inverse for this matrix, the outcome agreed over the ranks
-    L.coarse(P, true);
-    if ((rc = parts_coarse_agree(P, "c8_krylov_solve_parts")) != C8_OK) return rc;
-  }
-  if (multi) {  // A_1 over all parts, every A_l below it and the inverse of the last one, the outcome agreed over the ranks
+  if (coarse) {  // A_1 over all parts, every A_l below it and the inverse of the last one, the outcome agreed over the ranks
     L.levels(P, -1);
     if ((rc = parts_levels_agree(P, "c8_krylov_solve_parts")) != C8_OK) return rc;
   }
@@ -1503,48 +1509,40 @@ int c8_krylov_aggregate_base(c8_ctx* c, int32_t* base, int32_t* total_aggregates
   return C8_OK;
 }
 
+// The dense copy of A_level of a list of one part: the code behind c8_krylov_level_matrix (multi: the levels of
+// C8_PRECOND_MULTILEVEL) and c8_krylov_coarse_matrix (the two-level list, level 1)
+static int level_matrix(c8_ctx* c, const c8_system* sys, bool multi, int32_t level, int32_t* n_level, double* out_host, char const* who) {
+  int rc = multi ? multilevel_refusals(c, who) : coarse_refusals(c, who);
+  if (rc != C8_OK) return rc;
+  std::vector<c8_kry_level> const& lv = multi ? c->kry_levels : c->kry_agg_levels;
+  int const nc = coarse_columns(c);
+  if (multi && (rc = level_matrix_refusals(lv, level, nc)) != C8_OK) return rc;
+  *n_level = lv[level - 1].n * nc;
+  if (!out_host) return C8_OK;
+  Launchers L;
+  if (!launchers_of(c, &L)) return fail(C8_ERR_UNSUPPORTED, std::string(who) + ": no kernels for this number of dimensions and residuals");
+  Solve q{};
+  q.c = c;
+  q.nn = c->mesh.nnodes;
+  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
+  use_levels(q, multi);
+  if ((rc = L.levels(q, level)) != C8_OK) return rc;
+  std::vector<double> blocks;
+  C8_HIP(level_copy_start(c, lv, level, nc, out_host, &blocks));
+  C8_HIP(hipStreamSynchronize(c->stream));
+  level_copy_finish(lv, level, nc, out_host, blocks);
+  return C8_OK;
+}
+
 int c8_krylov_coarse_matrix(c8_ctx* c, const c8_system* sys, int32_t* n_coarse, double* out_host) {
   if (!c || !sys || !n_coarse) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null argument");
   bool const two = c->nres == 2;
   if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
     return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: null array in the system");
-  if (c->halo && (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS)) {  // collective: the global A_c, the same on every rank
-    Parts P = parts_of(c);
-    if (P.q.nn <= 0) return fail(C8_ERR_ARG, "c8_krylov_coarse_matrix: empty mesh");
-    int rcp = out_host ? parts_coarse_prepare(c, P, "c8_krylov_coarse_matrix") : parts_coarse_refusals(c, P, "c8_krylov_coarse_matrix");
-    if (rcp != C8_OK) return rcp;
-    int const n = (int)c->kry_pc_total * coarse_columns(c), lda = (n + 1) & ~1;
-    *n_coarse = n;
-    if (!out_host) return C8_OK;
-    P.q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
-    if (c->ndims == 3 && two) parts_coarse_setup<3, 2, 16>(P, false);
-    else if (c->ndims == 2 && two) parts_coarse_setup<2, 2, 8>(P, false);
-    else if (c->ndims == 2 && !two) parts_coarse_setup<2, 1, 8>(P, false);
-    else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_coarse_matrix: no kernels for this number of dimensions and residuals");
-    if (!P.failed)
-      P.hip(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
-                             hipMemcpyDeviceToHost, c->stream), "hipMemcpy2DAsync");
-    if (!P.failed) P.hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    return parts_coarse_agree(P, "c8_krylov_coarse_matrix");
-  }
-  int rc = coarse_refusals(c, "c8_krylov_coarse_matrix");
-  if (rc != C8_OK) return rc;
-  int const n = c->kry_nagg * coarse_columns(c), lda = (n + 1) & ~1;
-  *n_coarse = n;
-  if (!out_host) return C8_OK;
-  Solve q{};
-  q.c = c;
-  q.nn = c->mesh.nnodes;
-  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
-  if (c->ndims == 3 && two) rc = coarse_setup<3, 2, 16>(q, false);
-  else if (c->ndims == 2 && two) rc = coarse_setup<2, 2, 8>(q, false);
-  else if (c->ndims == 2 && !two) rc = coarse_setup<2, 1, 8>(q, false);
-  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_coarse_matrix: no kernels for this number of dimensions and residuals");
-  if (rc != C8_OK) return rc;
-  C8_HIP(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
-                          hipMemcpyDeviceToHost, c->stream));
-  C8_HIP(hipStreamSynchronize(c->stream));
-  return C8_OK;
+  // level 1 of the two-level list, whichever kind is selected; over parts collective: the global A_c, the same on every rank
+  if (c->halo && (c->kry_precond == C8_PRECOND_TWO_LEVEL_PARTS || c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS))
+    return parts_level_matrix(c, sys, false, 1, n_coarse, out_host, "c8_krylov_coarse_matrix");
+  return level_matrix(c, sys, false, 1, n_coarse, out_host, "c8_krylov_coarse_matrix");
 }
 
 int c8_krylov_set_multilevel(c8_ctx* c, int32_t coarse_max, int32_t max_levels) {
@@ -1562,7 +1560,7 @@ int c8_krylov_levels(c8_ctx* c, int32_t* num_levels) {
   if (!c || !num_levels) return fail(C8_ERR_ARG, "c8_krylov_levels: null argument");
   if (c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) {  // collective at the first use (reported above the cap too)
     Parts P = parts_of(c);
-    int const rcp = parts_levels_build(c, P, "c8_krylov_levels");
+    int const rcp = parts_levels_build(c, P, "c8_krylov_levels", true);
     if (rcp != C8_OK) return rcp;
     *num_levels = (int32_t)c->kry_pl_levels.size() + 1;
     return C8_OK;
@@ -1584,7 +1582,7 @@ int c8_krylov_level(c8_ctx* c, int32_t level, int32_t* num_nodes, const int32_t*
   int rc;
   if (parts) {  // (collective at the first use)
     Parts P = parts_of(c);
-    rc = parts_levels_build(c, P, "c8_krylov_level");
+    rc = parts_levels_build(c, P, "c8_krylov_level", true);
   } else rc = build_levels(c);
   if (rc != C8_OK) return rc;
   std::vector<c8_kry_level> const& lv = parts ? c->kry_pl_levels : c->kry_levels;
@@ -1614,45 +1612,9 @@ int c8_krylov_level_matrix(c8_ctx* c, const c8_system* sys, int32_t level, int32
   bool const two = c->nres == 2;
   if (!sys->A[0][0] || (two && (!sys->A[0][1] || !sys->A[1][0] || !sys->A[1][1])))
     return fail(C8_ERR_ARG, "c8_krylov_level_matrix: null array in the system");
-  if (c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS) return parts_level_matrix(c, sys, level, n_level, out_host);  // (collective)
-  int rc = multilevel_refusals(c, "c8_krylov_level_matrix");
-  if (rc != C8_OK) return rc;
-  int const nl = (int)c->kry_levels.size(), nc = coarse_columns(c);
-  if (level < 1 || level > nl)
-    return fail(C8_ERR_ARG, "c8_krylov_level_matrix: level " + std::to_string(level) + " is not one of the levels 1 .. " + std::to_string(nl));
-  c8_kry_level const& L = c->kry_levels[level - 1];
-  long long const nlong = (long long)L.n * nc;
-  if (nlong > COARSE_CAP)
-    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_level_matrix: level " + std::to_string(level) + " has " + std::to_string(nlong) +
-                                    " unknowns: a dense copy is refused above the cap of " + std::to_string(COARSE_CAP));
-  int const n = (int)nlong;
-  *n_level = n;
-  if (!out_host) return C8_OK;
-  Solve q{};
-  q.c = c;
-  q.nn = c->mesh.nnodes;
-  q.A = Blocks{sys->A[0][0], sys->A[0][1], sys->A[1][0], sys->A[1][1]};
-  if (c->ndims == 3 && two) rc = multilevel_setup<3, 2, 16>(q, level);
-  else if (c->ndims == 2 && two) rc = multilevel_setup<2, 2, 8>(q, level);
-  else if (c->ndims == 2 && !two) rc = multilevel_setup<2, 1, 8>(q, level);
-  else return fail(C8_ERR_UNSUPPORTED, "c8_krylov_level_matrix: no kernels for this number of dimensions and residuals");
-  if (rc != C8_OK) return rc;
-  if (level == nl) {
-    int const lda = (n + 1) & ~1;
-    C8_HIP(hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
-                            hipMemcpyDeviceToHost, c->stream));
-    C8_HIP(hipStreamSynchronize(c->stream));
-    return C8_OK;
-  }
-  std::vector<double> blocks(L.ga.size() * nc * nc);  // the block-sparse level, spread over the dense copy on the host
-  C8_HIP(hipMemcpyAsync(blocks.data(), L.d_A, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  C8_HIP(hipStreamSynchronize(c->stream));
-  std::fill(out_host, out_host + (size_t)n * n, 0.);
-  for (int i = 0; i < L.n; ++i)
-    for (int32_t e = L.gp[i]; e < L.gp[i + 1]; ++e)
-      for (int r = 0; r < nc; ++r)
-        for (int k = 0; k < nc; ++k) out_host[(size_t)(i * nc + r) * n + (size_t)L.ga[e] * nc + k] = blocks[((size_t)e * nc + r) * nc + k];
-  return C8_OK;
+  if (c->halo && c->kry_precond == C8_PRECOND_MULTILEVEL_PARTS)
+    return parts_level_matrix(c, sys, true, level, n_level, out_host, "c8_krylov_level_matrix");  // (collective)
+  return level_matrix(c, sys, true, level, n_level, out_host, "c8_krylov_level_matrix");
 }
 
 int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const v[2], double* const y[2]) {
@@ -1670,7 +1632,7 @@ int c8_krylov_precondition(c8_ctx* c, const c8_system* sys, const double* const 
 
 void c8_krylov_release(c8_ctx* c) {
   free_levels(c);
-  free_level_list(c->kry_pl_levels);
+  free_level_list(c->kry_pl_levels);  // (kry_agg_levels and kry_pc_levels hold no device buffers)
   if (c->kry_rocblas) (void)rocblas_destroy_handle((rocblas_handle)c->kry_rocblas);
   c->kry_rocblas = nullptr;
 }

@@ -1,17 +1,21 @@
-// c8_krylov_coarse.hpp -- the coarse level of the two-level preconditioner of the device solve (C8_PRECOND_TWO_LEVEL in
-// include/c8.h).  Included by c8_krylov.hip inside its unnamed namespace, after the kernels of the
-// one-level solve (TPB, Blocks, KryScalars, xcd_block, grow, Solve; rocSOLVER's header is included there).
+// c8_krylov_coarse.hpp -- what the four aggregation preconditioners of the device solve share between level 0 and level 1
+// (C8_PRECOND_TWO_LEVEL, C8_PRECOND_MULTILEVEL and their forms over parts in include/c8.h; DESIGN.md sections 13d to 13h).
+// Included by c8_krylov.hip inside its unnamed namespace, after the kernels of the one-level solve (TPB, Blocks, KryScalars,
+// xcd_block, grow, Solve; rocSOLVER's header is included there).
 //
-//   aggregates   three passes over the host node graph, once per context (build_aggregates); the device mirror holds the
-//                aggregate of every node, the node list and the neighbour list of every aggregate, and for every entry of
-//                the node graph the position of the column's aggregate in the neighbour list of the row's aggregate
+//   aggregates   three passes over a host node graph (aggregate_graph); the device mirror holds the aggregate of every node,
+//                the node list and the neighbour list of every aggregate, and for every entry of the node graph the position
+//                of the column's aggregate in the neighbour list of the row's aggregate
 //   P            never stored: aggregate id, the node's offset from the aggregate's centroid, the constrained-row flags
-//   set-up       k_constrained (flags) -> k_galerkin (A_c = P^T A P, dense, row-major, leading dimension lda) ->
-//                coarse_invert (in place) -> k_coarse_check; every solve, because the matrix changes every Newton iteration
-//   apply        k_restrict (r_c = P^T v) -> k_coarse_apply (e = A_c^-1 r_c) -> k_prolong (x = P e), then the sweeps of
-//                k_sgs_color started from this x
-// Every sum has a fixed order and no kernel uses a floating-point atomic.  The multilevel kind (c8_krylov_multilevel.hpp) uses
-// the same aggregation (aggregate_graph) on every level, these kernels between levels 0 and 1, and the dense solve on its last level.
+//   level 0      one descriptor (Level0) for one part and for a part among several: the tables, the first global id of the
+//                part's aggregates (base), their count, the count over all parts, the owned nodes.  One part: base 0,
+//                total = nagg, nown = nnodes.  The kernels take these and are the same for both.
+//   set-up       k_constrained (flags) -> k_galerkin (A_1 = P^T A P: dense, row-major, leading dimension lda, or block-sparse)
+//   apply        k_restrict (r_1 = P^T v) ... k_prolong (x = P e_1); the sweeps of k_sgs_color start from this x
+//   last level   dense: coarse_invert (in place) -> k_coarse_check at set-up, k_coarse_apply (e = A^-1 r) in the apply
+// Over parts every entry of A_1 and of r_1 is written by one rank and zero on the others, so that the all-reduce between
+// the ranks is exact.  Every sum has a fixed order and no kernel uses a floating-point atomic.  The block levels below
+// level 1 and the single-part host path are in c8_krylov_multilevel.hpp, the host path over parts in c8_krylov_parts_levels.hpp.
 constexpr int COARSE_CAP = 8192;          // n_coarse of the dense coarse solve: a 512 MB inverse
 constexpr size_t GALERKIN_LDS = 64 * 1024;  // largest tile of k_galerkin
 
@@ -40,9 +44,11 @@ __device__ __forceinline__ double p_entry(int r, int c, double const* d) {
 }
 
 // ---- constrained rows: bit r of flags[node] is set when every off-diagonal entry of the node's equation r is exactly 0
-// in all blocks (the rows c8_apply_dirichlet leaves).  Lane mapping of k_spmv, an OR over the node's G lanes.
+// in all blocks (the rows c8_apply_dirichlet leaves).  Lane mapping of k_spmv, an OR over the node's G lanes.  Rows
+// 0 .. n_rows - 1: all nodes of one part, or the owned nodes of a part among several (over the whole row: off-part columns
+// included).
 template <int ND, int NRES, int G>
-__global__ void __launch_bounds__(TPB) k_constrained(int nn, int nblocks, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj,
+__global__ void __launch_bounds__(TPB) k_constrained(int n_rows, int nblocks, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj,
                                                      Blocks A, int32_t* __restrict__ flags) {
   constexpr int NB = ND + (NRES == 2 ? 1 : 0);
   constexpr int NPB = TPB / G;
@@ -50,7 +56,7 @@ __global__ void __launch_bounds__(TPB) k_constrained(int nn, int nblocks, int32_
   if (lb >= nblocks) return;
   int const node = lb * NPB + threadIdx.x / G, lane = threadIdx.x % G;
   int nz = 0;  // bit r: equation r has a non-zero off-diagonal entry
-  if (node < nn) {
+  if (node < n_rows) {
     int64_t const np = nodeptr[node];
     int const deg = (int)(nodeptr[node + 1] - np);
     for (int k = lane; k < deg; k += G) {
@@ -73,7 +79,7 @@ __global__ void __launch_bounds__(TPB) k_constrained(int nn, int nblocks, int32_
     }
   }
   for (int o = G / 2; o > 0; o >>= 1) nz |= __shfl_xor(nz, o, G);
-  if (node < nn && lane == 0) flags[node] = ~nz & ((1 << NB) - 1);
+  if (node < n_rows && lane == 0) flags[node] = ~nz & ((1 << NB) - 1);
 }
 
 struct AggTables {  // device mirror of the aggregates (c8_ctx::d_kry_agg and its offsets)
@@ -81,18 +87,30 @@ struct AggTables {  // device mirror of the aggregates (c8_ctx::d_kry_agg and it
   double const* off;  // [nnodes][ND]: x_i - centroid of the node's aggregate
   int32_t const* flags;
 };
+// Level 0 as the launches between level 0 and level 1 see it.  Over parts the tables are local-sized (owned nodes, then the
+// copies with the owners' P imported), T.agg_of and T.nbr hold GLOBAL aggregate ids, T.ptr / T.nodes / T.nbr_ptr the part's
+// own aggregates counted from 0.
+struct Level0 {
+  AggTables T;
+  int base, nagg, total;  // first global id of the part's aggregates, their number, the number over all parts
+  int nown;               // nodes whose rows the part owns: the first nown of its nodes
+  int max_nbr;            // most neighbouring aggregates of one aggregate (itself included): the tile of k_galerkin
+};
 
-// ---- A_c = P^T A P.  One workgroup owns the block row of aggregate I: NC rows of A_c, its tile in LDS has one NC x NC
-// block per neighbouring aggregate (tile[r][slot * NC + c], neighbours in ascending id).  A work item owns the tile columns
-// q = slot * NC + c, q = thread, thread + TPB, ...: it walks the aggregate's nodes in ascending id and each node's graph
-// row in column order, and for the entries whose column node lies in the aggregate of `slot` adds P_i^T (A_ij P_j[:, c])
-// to its NC tile entries -- one owner per entry, the sum of an entry in one fixed order.  A column of P that is zero (every
-// row of the mode constrained, or a one-node aggregate's rotation) gets a unit diagonal.  The tile is then written to
-// A_c, every entry once; the other entries of A_c are the zeros of the memset before the launch.  SPARSE (the multilevel
-// kind, c8_krylov_multilevel.hpp): the tile goes to the block-sparse A_1 instead, the NC x NC block of neighbour `slot` to
-// graph entry nbr_ptr[I] + slot of level 1; the sums are the same.
+// ---- the part's block rows of A_1 = P^T A P.  One workgroup owns the block row of the part's aggregate I (global id
+// base + I): NC rows of A_1, its tile in LDS has one NC x NC block per neighbouring aggregate on any part
+// (tile[r][slot * NC + c], T.nbr in ascending global id).  A work item owns the tile columns q = slot * NC + c,
+// q = thread, thread + TPB, ...: it walks the aggregate's nodes in ascending id and each node's graph row in column order,
+// and for the entries whose column node lies in the aggregate of `slot` adds P_i^T (A_ij P_j[:, c]) to its NC tile entries
+// -- one owner per entry, the sum of an entry in one fixed order.  P_j of a ghost or phantom column comes from the imported
+// entries of T.agg_of / T.off / T.flags.  A column of P that is zero (every row of the mode constrained, or a one-node
+// aggregate's rotation) gets a unit diagonal, the owner's.  Output, every entry once:
+//   dense    rows (base + I) * NC ... of the row-major matrix; the other entries are the zeros of the memset before the launch
+//   SPARSE   the NC x NC block of neighbour `slot` to graph entry nbr_ptr_global[base + I] + slot of the block-sparse A_1.
+//            The part's aggregates are consecutive rows of that graph and T.nbr_ptr counts the same lists from the part's
+//            first row, so the entry is nbr_ptr_global[base] + T.nbr_ptr[I] + slot and Ac points at entry nbr_ptr_global[base].
 template <int ND, int NRES, bool SPARSE = false>
-__global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj, Blocks A,
+__global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int base, int32_t const* __restrict__ nodeptr, int32_t const* __restrict__ nodeadj, Blocks A,
                                                   double* __restrict__ Ac, int lda) {
   constexpr int NB = CoarseDims<ND, NRES>::NB, NC = CoarseDims<ND, NRES>::NC;
   extern __shared__ double tile[];
@@ -101,7 +119,7 @@ __global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __
   int const W = (T.nbr_ptr[I + 1] - b0) * NC;
   for (int q = threadIdx.x; q < W; q += TPB) {
     int const sl = q / NC, c = q % NC;
-    bool const own = T.nbr[b0 + sl] == I;
+    bool const own = T.nbr[b0 + sl] == base + I;
     bool colnz = false;
     double acc[NC];
 #pragma unroll
@@ -121,7 +139,7 @@ __global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __
       int const deg = (int)(nodeptr[node + 1] - np);
       for (int k = 0; k < deg; ++k) {
         if (T.slot[np + k] != sl) continue;
-        int const cn = nodeadj[np + k];
+        int const cn = nodeadj[np + k];  // owned, ghost or phantom: the tables are local-sized
         int const fj = T.flags[cn];
         double dj[ND], pj[NB], w[NB];
 #pragma unroll
@@ -161,23 +179,26 @@ __global__ void __launch_bounds__(TPB) k_galerkin(AggTables T, int32_t const* __
   for (int idx = threadIdx.x; idx < NC * W; idx += TPB) {
     int const r = idx / W, q = idx % W;
     if (SPARSE) Ac[((size_t)(b0 + q / NC) * NC + r) * NC + q % NC] = tile[idx];
-    else Ac[(size_t)(I * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
+    else Ac[(size_t)((base + I) * NC + r) * lda + (size_t)T.nbr[b0 + q / NC] * NC + q % NC] = tile[idx];
   }
 }
 
-// ---- r_c = P^T v: one wavefront per aggregate, lane l takes the nodes l, l + 64, ... of the aggregate's list, then a
-// fixed butterfly over the lanes
+// ---- r_1 = P^T v over all aggregates of all parts: one wavefront per GLOBAL aggregate.  Those of this part
+// (base <= id < base + nagg): lane l takes the nodes l, l + 64, ... of the aggregate's list, then a fixed butterfly over
+// the lanes.  The others get the zeros the all-reduce needs.  v is local-sized (p at nn * ND).
 template <int ND, int NRES>
-__global__ void __launch_bounds__(TPB) k_restrict(int nagg, AggTables T, int nn, double const* __restrict__ v, double* __restrict__ rc,
-                                                  KryScalars const* S) {
+__global__ void __launch_bounds__(TPB) k_restrict(int ntotal, int base, int nagg, AggTables T, int nn, double const* __restrict__ v,
+                                                  double* __restrict__ rc, KryScalars const* S) {
   constexpr int NB = CoarseDims<ND, NRES>::NB, NC = CoarseDims<ND, NRES>::NC;
   if (S->stop) return;
-  int const I = blockIdx.x * (TPB / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+  int const gI = blockIdx.x * (TPB / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+  int const I = gI - base;
+  bool const mine = gI < ntotal && I >= 0 && I < nagg;
   size_t const n0 = (size_t)nn * ND;
   double acc[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) acc[c] = 0.;
-  if (I < nagg) {
+  if (mine) {
     for (int a = T.ptr[I] + lane; a < T.ptr[I + 1]; a += 64) {
       int const node = T.nodes[a];
       int const f = T.flags[node];
@@ -195,20 +216,22 @@ __global__ void __launch_bounds__(TPB) k_restrict(int nagg, AggTables T, int nn,
 #pragma unroll
   for (int c = 0; c < NC; ++c)
     for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
-  if (I < nagg && lane == 0) {
+  if (gI < ntotal && lane == 0) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) rc[(size_t)I * NC + c] = acc[c];
+    for (int c = 0; c < NC; ++c) rc[(size_t)gI * NC + c] = acc[c];
   }
 }
 
-// ---- e = A_c^-1 r_c, the dense row-major inverse: one wavefront per row, 16-byte loads (lda is even, the padding entries
-// of a row and of r_c are zero), a fixed butterfly over the lanes
-__global__ void __launch_bounds__(TPB) k_coarse_apply(int n, int lda, double const* __restrict__ Ainv, double const* __restrict__ rc,
-                                                      double* __restrict__ e, KryScalars const* S) {
+// ---- rows [row0, row0 + nrows) of e = A^-1 r, the dense row-major inverse of the last level: one wavefront per row,
+// 16-byte loads (lda is even, the padding entries of a row and of r are zero), a fixed butterfly over the lanes.  Over
+// parts with level 1 the last level a rank forms the rows of its own aggregates only: the others are not its to prolong.
+__global__ void __launch_bounds__(TPB) k_coarse_apply(int row0, int nrows, int lda, double const* __restrict__ Ainv,
+                                                      double const* __restrict__ rc, double* __restrict__ e, KryScalars const* S) {
   if (S->stop) return;
-  int const row = blockIdx.x * (TPB / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+  int const k = blockIdx.x * (TPB / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+  int const row = row0 + k;
   double s = 0.;
-  if (row < n) {
+  if (k < nrows) {
     double2 const* a = (double2 const*)(Ainv + (size_t)row * lda);
     double2 const* x = (double2 const*)rc;
     for (int j = lane; j < lda / 2; j += 64) {
@@ -218,19 +241,20 @@ __global__ void __launch_bounds__(TPB) k_coarse_apply(int n, int lda, double con
     }
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (row < n && lane == 0) e[row] = s;
+  if (k < nrows && lane == 0) e[row] = s;
 }
 
-// ---- x = P e, one work item per node: the start of the Gauss-Seidel sweeps in the place of x = 0
+// ---- x = P e on the owned nodes of a local-sized vector (the p segment starts at nn * ND), one work item per node: the
+// start of the Gauss-Seidel sweeps in the place of x = 0.  T.agg_of indexes e: global ids over parts.
 template <int ND, int NRES>
-__global__ void __launch_bounds__(TPB) k_prolong(int nn, int nblocks, AggTables T, double const* __restrict__ e, double* __restrict__ x,
+__global__ void __launch_bounds__(TPB) k_prolong(int nown, int nn, int nblocks, AggTables T, double const* __restrict__ e, double* __restrict__ x,
                                                  KryScalars const* S) {
   constexpr int NB = CoarseDims<ND, NRES>::NB, NC = CoarseDims<ND, NRES>::NC;
   if (S->stop) return;
   int const lb = xcd_block(blockIdx.x, nblocks);
   if (lb >= nblocks) return;
   int const node = lb * TPB + threadIdx.x;
-  if (node >= nn) return;
+  if (node >= nown) return;
   int const f = T.flags[node];
   double const* ea = e + (size_t)T.agg_of[node] * NC;
   double d[ND], ev[NC];
@@ -270,6 +294,30 @@ struct Aggregates {
   std::vector<double> off;                            // [n][nd] node - centroid of its aggregate
   std::vector<double> centroid;                       // [nagg][3]
 };
+// The neighbouring aggregates of every aggregate of H (ascending id, itself included) and the slot of every entry of the
+// graph (gp, ga) in the list of its row's aggregate, from H.agg (the aggregate of every node of the graph, ids below
+// `nids`) and the node lists H.ptr, H.nodes of the H.nagg aggregates whose rows are walked.  aggregate_graph: local ids,
+// all of them.  Over parts: global ids at all local nodes, the whole owned rows of the rank's own aggregates.
+void neighbour_lists(Aggregates& H, int nids, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga) {
+  std::vector<int32_t> const &agg = H.agg, &ptr = H.ptr, &nodes = H.nodes;
+  std::vector<int32_t>&nbr_ptr = H.nbr_ptr, &nbr = H.nbr, &slot = H.slot;
+  std::vector<int32_t> where(nids, -1);
+  nbr.clear(), H.max_nbr = 0;
+  nbr_ptr.assign(H.nagg + 1, 0), slot.assign(ga.size(), 0);
+  for (int a = 0; a < H.nagg; ++a) {
+    size_t const lo = nbr.size();
+    for (int k = ptr[a]; k < ptr[a + 1]; ++k)
+      for (int32_t e = gp[nodes[k]]; e < gp[nodes[k] + 1]; ++e)
+        if (where[agg[ga[e]]] != a) { where[agg[ga[e]]] = a; nbr.push_back(agg[ga[e]]); }
+    std::sort(nbr.begin() + lo, nbr.end());
+    nbr_ptr[a + 1] = (int32_t)nbr.size();
+    H.max_nbr = std::max(H.max_nbr, (int)(nbr.size() - lo));
+    for (int k = ptr[a]; k < ptr[a + 1]; ++k)
+      for (int32_t e = gp[nodes[k]]; e < gp[nodes[k] + 1]; ++e)
+        slot[e] = (int32_t)(std::lower_bound(nbr.begin() + lo, nbr.end(), agg[ga[e]]) - (nbr.begin() + lo));
+  }
+}
+
 Aggregates aggregate_graph(int nn, int nd, std::vector<int32_t> const& gp, std::vector<int32_t> const& ga, double const* x) {
   Aggregates H;
   std::vector<int32_t>& agg = H.agg;
@@ -309,23 +357,8 @@ Aggregates aggregate_graph(int nn, int nd, std::vector<int32_t> const& gp, std::
       H.centroid[(size_t)a * 3 + d] = mean;
       for (int k = ptr[a]; k < ptr[a + 1]; ++k) H.off[(size_t)nodes[k] * nd + d] = x[(size_t)nodes[k] * 3 + d] - mean;
     }
-  // neighbouring aggregates of every aggregate (ascending id, itself included) and the slot of every graph entry
-  std::vector<int32_t>&nbr_ptr = H.nbr_ptr, &nbr = H.nbr, &slot = H.slot;
-  std::vector<int32_t> where(nagg, -1);
-  nbr_ptr.assign(nagg + 1, 0), slot.assign(ga.size(), 0);
-  for (int a = 0; a < nagg; ++a) {
-    size_t const lo = nbr.size();
-    for (int k = ptr[a]; k < ptr[a + 1]; ++k)
-      for (int32_t e = gp[nodes[k]]; e < gp[nodes[k] + 1]; ++e)
-        if (where[agg[ga[e]]] != a) { where[agg[ga[e]]] = a; nbr.push_back(agg[ga[e]]); }
-    std::sort(nbr.begin() + lo, nbr.end());
-    nbr_ptr[a + 1] = (int32_t)nbr.size();
-    H.max_nbr = std::max(H.max_nbr, (int)(nbr.size() - lo));
-    for (int k = ptr[a]; k < ptr[a + 1]; ++k)
-      for (int32_t e = gp[nodes[k]]; e < gp[nodes[k] + 1]; ++e)
-        slot[e] = (int32_t)(std::lower_bound(nbr.begin() + lo, nbr.end(), agg[ga[e]]) - (nbr.begin() + lo));
-  }
   H.nagg = nagg;
+  neighbour_lists(H, nagg, gp, ga);
   return H;
 }
 
@@ -346,8 +379,9 @@ int upload_aggregates(Aggregates const& H, int32_t** d_agg, size_t at[6], double
   return C8_OK;
 }
 
-// The aggregates of the context's node graph, once per context, and their device mirror; the graph and the positions of
-// level 1 (the neighbour lists and the centroids) stay on the host for the multilevel kind.
+// The aggregates of the context's node graph, once per context, and their device mirror.  Level 1 (its graph is the
+// neighbour lists, its positions the centroids) is the one entry of the two-level kind's list of levels, kry_agg_levels;
+// the multilevel kind copies it and builds on the copy (build_levels).
 int build_aggregates(c8_ctx* c) {
   if (c->kry_nagg >= 0) return C8_OK;
   int const nn = c->mesh.nnodes;
@@ -360,16 +394,21 @@ int build_aggregates(c8_ctx* c) {
   if (rc != C8_OK) return rc;
   C8_HIP(hipMalloc((void**)&c->d_kry_cflags, (size_t)nn * sizeof(int32_t)));
   c->kry_agg_of = std::move(H.agg);
-  c->kry_agg_nbr_ptr = std::move(H.nbr_ptr), c->kry_agg_nbr = std::move(H.nbr), c->kry_agg_x = std::move(H.centroid);
+  c->kry_agg_levels.assign(1, c8_kry_level{});
+  c8_kry_level& L1 = c->kry_agg_levels[0];
+  L1.n = H.nagg;
+  L1.gp = std::move(H.nbr_ptr), L1.ga = std::move(H.nbr), L1.x = std::move(H.centroid);
   c->kry_agg_max_nbr = H.max_nbr;
   c->kry_nagg = H.nagg;
   return C8_OK;
 }
 
-inline AggTables agg_tables(c8_ctx const* c) {
+// level 0 of one part (no halo): the tables of build_aggregates
+inline Level0 level0(c8_ctx const* c) {
   int32_t const* b = c->d_kry_agg;
   size_t const* o = c->kry_agg_at;
-  return AggTables{b + o[0], b + o[1], b + o[2], b + o[3], b + o[4], b + o[5], c->d_kry_agg_off, c->d_kry_cflags};
+  return Level0{AggTables{b + o[0], b + o[1], b + o[2], b + o[3], b + o[4], b + o[5], c->d_kry_agg_off, c->d_kry_cflags},
+                0, c->kry_nagg, c->kry_nagg, c->mesh.nnodes, c->kry_agg_max_nbr};
 }
 
 // what a call must refuse before any device work of the two-level kind: a halo, the cap of the dense coarse solve
@@ -405,58 +444,4 @@ int coarse_invert(c8_ctx* c, int n, int lda, double* A, int32_t* ipiv, int32_t* 
   if (st != rocblas_status_success)
     return fail(C8_ERR_DEVICE, "c8_krylov: the dense inverse of the coarse matrix failed (rocSOLVER status " + std::to_string((int)st) + ")");
   return C8_OK;
-}
-
-// The coarse level for the matrix of q, up to A_c (invert = false: c8_krylov_coarse_matrix) or to its checked inverse.
-// Needs coarse_refusals() passed.
-template <int ND, int NRES, int G>
-int coarse_setup(Solve const& q, bool invert) {
-  constexpr int NC = CoarseDims<ND, NRES>::NC;
-  c8_ctx* c = q.c;
-  int const nagg = c->kry_nagg, n = nagg * NC, lda = (n + 1) & ~1;
-  size_t const lds = (size_t)c->kry_agg_max_nbr * NC * NC * sizeof(double);
-  if (lds > GALERKIN_LDS)
-    return fail(C8_ERR_UNSUPPORTED, "c8_krylov: an aggregate has " + std::to_string(c->kry_agg_max_nbr) +
-                                    " neighbouring aggregates: the block row of the coarse matrix does not fit the tile of k_galerkin");
-  int rc;
-  if ((rc = grow(&c->d_kry_Ac, &c->kry_Ac_n, (size_t)n * lda)) != C8_OK) return rc;
-  if ((rc = grow(&c->d_kry_cvec, &c->kry_cvec_n, 2 * (size_t)lda)) != C8_OK) return rc;
-  if ((rc = grow(&c->d_kry_ipiv, &c->kry_ipiv_n, (size_t)n + 4)) != C8_OK) return rc;
-  hipStream_t const st = c->stream;
-  int32_t* info = c->d_kry_ipiv + n;  // getrf, getri, first row of the inverse that is not finite
-  int32_t h_info[3] = {0, 0, INT_MAX};
-  C8_HIP(hipMemcpyAsync(info, h_info, sizeof(h_info), hipMemcpyHostToDevice, st));
-  C8_HIP(hipMemsetAsync(c->d_kry_Ac, 0, (size_t)n * lda * sizeof(double), st));
-  C8_HIP(hipMemsetAsync(c->d_kry_cvec, 0, 2 * (size_t)lda * sizeof(double), st));
-  int const nb_g = (q.nn + TPB / G - 1) / (TPB / G);
-  hipLaunchKernelGGL((k_constrained<ND, NRES, G>), dim3(xcd_grid(nb_g)), dim3(TPB), 0, st, q.nn, nb_g, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_cflags);
-  C8_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_galerkin<ND, NRES>), dim3(nagg), dim3(TPB), lds, st, agg_tables(c), c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_Ac, lda);
-  C8_HIP(hipGetLastError());
-  if (!invert) return C8_OK;
-  if ((rc = coarse_invert(c, n, lda, c->d_kry_Ac, c->d_kry_ipiv, info)) != C8_OK) return rc;
-  int const nb_c = (int)std::min<size_t>(((size_t)n * lda + TPB - 1) / TPB, (size_t)UPDATE_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_coarse_check, dim3(nb_c), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, info + 2);
-  C8_HIP(hipGetLastError());
-  C8_HIP(hipMemcpyAsync(h_info, info, sizeof(h_info), hipMemcpyDeviceToHost, st));
-  C8_HIP(hipStreamSynchronize(st));
-  int const bad = h_info[0] > 0 ? h_info[0] - 1 : h_info[1] > 0 ? h_info[1] - 1 : h_info[2] != INT_MAX ? h_info[2] : -1;
-  if (bad >= 0)
-    return fail(C8_ERR_ARG, "c8_krylov: the coarse matrix of the two-level preconditioner is singular or not finite at aggregate " +
-                            std::to_string(bad / NC) + " (coarse row " + std::to_string(bad) + " of " + std::to_string(n) + ")");
-  return C8_OK;
-}
-
-// x = P A_c^-1 P^T rhs
-template <int ND, int NRES>
-hipError_t launch_coarse(Solve const& q, double const* rhs, double* x) {
-  constexpr int NC = CoarseDims<ND, NRES>::NC;
-  c8_ctx const* c = q.c;
-  int const nagg = c->kry_nagg, n = nagg * NC, lda = (n + 1) & ~1, wpb = TPB / 64;
-  AggTables const T = agg_tables(c);
-  double *rc = c->d_kry_cvec, *e = c->d_kry_cvec + lda;
-  hipLaunchKernelGGL((k_restrict<ND, NRES>), dim3((nagg + wpb - 1) / wpb), dim3(TPB), 0, c->stream, nagg, T, q.nn, rhs, rc, q.S);
-  hipLaunchKernelGGL(k_coarse_apply, dim3((n + wpb - 1) / wpb), dim3(TPB), 0, c->stream, n, lda, c->d_kry_Ac, rc, e, q.S);
-  hipLaunchKernelGGL((k_prolong<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, c->stream, q.nn, q.nb_node, T, e, x, q.S);
-  return hipGetLastError();
 }

@@ -1,19 +1,24 @@
-// c8_krylov_multilevel.hpp -- the levels below the first coarse level of the device solve's multilevel preconditioner
-// (C8_PRECOND_MULTILEVEL in include/c8.h).  Included by c8_krylov.hip inside its unnamed namespace,
+// c8_krylov_multilevel.hpp -- the block levels below level 1 of the aggregation preconditioners of the device solve, the
+// cycle over a list of levels, and the set-up and apply of the kinds of one part (C8_PRECOND_TWO_LEVEL: a list of one
+// level, C8_PRECOND_MULTILEVEL; DESIGN.md sections 13d, 13e, 13h).  Included by c8_krylov.hip inside its unnamed namespace,
 // after c8_krylov_coarse.hpp and launch_sgs.
 //
 //   levels    level 0 is the system (node blocks, the four CSR value arrays, the aggregates and kernels of
 //             c8_krylov_coarse.hpp).  Level l >= 1 has one node per aggregate of level l - 1 with NC unknowns; its graph is
 //             the neighbour list of those aggregates; its matrix is block-sparse over that graph, one row-major NC x NC block
-//             per graph entry (A[entry][r][c]), its vectors are node-major ([node][NC]).  The last level is dense: the
-//             matrix, inverse and vectors of the two-level kind (d_kry_Ac, d_kry_cvec, coarse_invert, k_coarse_apply).
+//             per graph entry (A[entry][r][c]), its vectors are node-major ([node][NC]).  The last level is dense
+//             (d_kry_Ac, d_kry_cvec, coarse_invert, k_coarse_apply).  A list lv holds level k + 1 in lv[k].
 //   P_l       l >= 1, never stored: the aggregate of a node, its offset d from the aggregate's centroid, the constrained
 //             flags of level l.  NC x NC block: identity, plus rotation m -> translation e_m x d (pb_entry).
-//   set-up    k_constrained -> k_galerkin (A_1, block-sparse here) -> per level l >= 1: k_level_setup (flags, inverses of the
-//             diagonal blocks) -> k_level_galerkin (A_l+1, block-sparse or dense) -> coarse_invert -> k_coarse_check
+//   set-up    k_constrained -> k_galerkin (A_1, dense when level 1 is the last, else block-sparse) -> per level l >= 1:
+//             k_level_setup (flags, inverses of the diagonal blocks) -> k_level_galerkin (A_l+1, block-sparse or dense) ->
+//             coarse_invert -> k_coarse_check
 //   apply     k_restrict, k_level_restrict ... -> k_coarse_apply -> per level upwards: k_level_prolong, the colour launches of
 //             k_level_sgs -> k_prolong; the sweeps of level 0 (launch_sgs) follow in the caller
-// Every sum has a fixed order and no kernel uses a floating-point atomic.
+// With one level the loops over the block levels are empty: the launches are k_constrained, k_galerkin, coarse_invert,
+// k_coarse_check and k_restrict, k_coarse_apply, k_prolong.  Every sum has a fixed order and no kernel uses a floating-point
+// atomic.  levels_begin, levels_form, levels_invert, levels_bad_row and launch_level_cycle serve the kinds over parts too
+// (c8_krylov_parts_levels.hpp), which keep an error discipline of their own.
 constexpr int LEVEL_G = 8;  // lanes per node of k_level_sgs
 
 // entry (r, c) of the block of P_l, l >= 1, before the constrained flags; d = x_a - centroid of the node's aggregate.  The
@@ -335,18 +340,14 @@ int extend_levels(c8_ctx* c, std::vector<c8_kry_level>& lv) {
 }
 
 // The levels below level 0 from the aggregates of level 0, once per setting of c8_krylov_set_multilevel: kry_levels[k] is
-// level k + 1.  Level 1 always exists (P_0 is the P of the two-level kind); the levels below it by extend_levels.
+// level k + 1.  Level 1 always exists: a copy of the two-level kind's one entry (host data only); the levels below it by
+// extend_levels.
 int build_levels(c8_ctx* c) {
   if (c->kry_ml_built) return C8_OK;
   free_levels(c);
   int rc = build_aggregates(c);
   if (rc != C8_OK) return rc;
-  c->kry_levels.emplace_back();
-  {
-    c8_kry_level& L1 = c->kry_levels.back();
-    L1.n = c->kry_nagg;
-    L1.gp = c->kry_agg_nbr_ptr, L1.ga = c->kry_agg_nbr, L1.x = c->kry_agg_x;
-  }
+  c->kry_levels = c->kry_agg_levels;
   if ((rc = extend_levels(c, c->kry_levels)) != C8_OK) return rc;
   c->kry_ml_built = true;
   return C8_OK;
@@ -380,8 +381,8 @@ int multilevel_refusals(c8_ctx* c, char const* who) {
   return C8_OK;
 }
 
-// The numeric set-up of a list of levels (lv[k] is level k + 1, the last one dense) in three steps, shared by the kind over
-// one part and the kind over parts (c8_krylov_parts_multilevel.hpp), which differ in how A_1 is formed between the first
+// The numeric set-up of a list of levels (lv[k] is level k + 1, the last one dense) in three steps, shared by the kinds of
+// one part and the kinds over parts (c8_krylov_parts_levels.hpp), which differ in how A_1 is completed between the first
 // two.  levels_begin: the buffers of the last level and the status words `info` (getrf, getri, first row of the inverse
 // that is not finite, then per level k + 1 its bad block), r_c and e zeroed.
 template <int NC>
@@ -436,22 +437,42 @@ int levels_invert(c8_ctx* c, std::vector<c8_kry_level> const& lv, int32_t* info,
 // ... the bad row of the last level in those words (-1: none)
 inline int levels_bad_row(std::vector<int32_t> const& h) { return h[0] > 0 ? h[0] - 1 : h[1] > 0 ? h[1] - 1 : h[2] != INT_MAX ? h[2] : -1; }
 
-// The hierarchy for the matrix of q: A_1 .. A_upto (upto < 0: all levels, then the checked inverse of the last one).
-// Needs multilevel_refusals() passed.
+// The part's block rows of A_1 for the matrix of q -- dense into d_kry_Ac when level 1 is the last level, else block-sparse
+// into lv[0].d_A from the part's first row.  The caller has zeroed the target and formed the flags.
+template <int ND, int NRES>
+hipError_t launch_level0_galerkin(Solve const& q) {
+  constexpr int NC = CoarseDims<ND, NRES>::NC;
+  c8_ctx const* c = q.c;
+  std::vector<c8_kry_level> const& lv = *q.lv;
+  Level0 const& l0 = q.l0;
+  if (l0.nagg <= 0) return hipSuccess;
+  size_t const lds = (size_t)l0.max_nbr * NC * NC * sizeof(double);
+  int const n = lv.back().n * NC, lda = (n + 1) & ~1;
+  if (lv.size() == 1)
+    hipLaunchKernelGGL((k_galerkin<ND, NRES, false>), dim3(l0.nagg), dim3(TPB), lds, c->stream, l0.T, l0.base, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_Ac, lda);
+  else
+    hipLaunchKernelGGL((k_galerkin<ND, NRES, true>), dim3(l0.nagg), dim3(TPB), lds, c->stream, l0.T, l0.base, c->d_nodeptr, c->d_nodeadj, q.A,
+                       lv[0].d_A + (size_t)lv[0].gp[l0.base] * NC * NC, 0);
+  return hipGetLastError();
+}
+
+// The levels of q (q.lv, q.l0: use_levels) for the matrix of q: A_1 .. A_upto (upto < 0: all levels, then the checked inverse
+// of the last one).  The two-level kind and the multilevel kind differ in the length of the list and in the wording of
+// their messages (q.multi).  Needs the kind's refusals passed.
 template <int ND, int NRES, int G>
-int multilevel_setup(Solve const& q, int upto) {
+int levels_setup(Solve const& q, int upto) {
   constexpr int NC = CoarseDims<ND, NRES>::NC;
   c8_ctx* c = q.c;
-  std::vector<c8_kry_level>& lv = c->kry_levels;
+  std::vector<c8_kry_level> const& lv = *q.lv;
   int const nl = (int)lv.size();  // level k + 1 is lv[k]; the last one is dense
   int const n = lv.back().n * NC, lda = (n + 1) & ~1;
   bool const invert = upto < 0;
   if (invert) upto = nl;
-  int worst = c->kry_agg_max_nbr;
+  int worst = q.l0.max_nbr;
   for (int k = 0; k + 1 < nl; ++k) worst = std::max(worst, lv[k].max_nbr);
   if ((size_t)worst * NC * NC * sizeof(double) > GALERKIN_LDS)
-    return fail(C8_ERR_UNSUPPORTED, "c8_krylov: an aggregate has " + std::to_string(worst) +
-                                    " neighbouring aggregates: the block row of a coarse matrix does not fit the tile of k_galerkin");
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov: an aggregate has " + std::to_string(worst) + " neighbouring aggregates: the block row of " +
+                                    (q.multi ? "a" : "the") + " coarse matrix does not fit the tile of k_galerkin");
   int rc;
   hipStream_t const st = c->stream;
   int32_t* info = nullptr;
@@ -460,13 +481,8 @@ int multilevel_setup(Solve const& q, int upto) {
   int const nb_g = (q.nn + TPB / G - 1) / (TPB / G);
   hipLaunchKernelGGL((k_constrained<ND, NRES, G>), dim3(xcd_grid(nb_g)), dim3(TPB), 0, st, q.nn, nb_g, c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_cflags);
   C8_HIP(hipGetLastError());
-  if (nl == 1 || upto >= nl) C8_HIP(hipMemsetAsync(c->d_kry_Ac, 0, (size_t)n * lda * sizeof(double), st));
-  size_t const lds = (size_t)c->kry_agg_max_nbr * NC * NC * sizeof(double);
-  if (nl == 1)
-    hipLaunchKernelGGL((k_galerkin<ND, NRES, false>), dim3(c->kry_nagg), dim3(TPB), lds, st, agg_tables(c), c->d_nodeptr, c->d_nodeadj, q.A, c->d_kry_Ac, lda);
-  else
-    hipLaunchKernelGGL((k_galerkin<ND, NRES, true>), dim3(c->kry_nagg), dim3(TPB), lds, st, agg_tables(c), c->d_nodeptr, c->d_nodeadj, q.A, lv[0].d_A, 0);
-  C8_HIP(hipGetLastError());
+  if (upto >= nl) C8_HIP(hipMemsetAsync(c->d_kry_Ac, 0, (size_t)n * lda * sizeof(double), st));
+  C8_HIP((launch_level0_galerkin<ND, NRES>(q)));
   if ((rc = levels_form<ND, NRES>(c, lv, upto, info)) != C8_OK) return rc;
   if (!invert) return C8_OK;
   if ((rc = levels_invert<NC>(c, lv, info, &h_info)) != C8_OK) return rc;
@@ -475,25 +491,37 @@ int multilevel_setup(Solve const& q, int upto) {
       return fail(C8_ERR_ARG, "c8_krylov: the diagonal block of aggregate " + std::to_string(h_info[3 + k]) + " on level " + std::to_string(k + 1) +
                               " of the multilevel preconditioner is singular or not finite");
   int const bad = levels_bad_row(h_info);
-  if (bad >= 0)
-    return fail(C8_ERR_ARG, "c8_krylov: the matrix of level " + std::to_string(nl) + " (the last) of the multilevel preconditioner is singular or not finite at aggregate " +
-                            std::to_string(bad / NC) + " (row " + std::to_string(bad) + " of " + std::to_string(n) + ")");
-  return C8_OK;
+  if (bad < 0) return C8_OK;
+  if (!q.multi)
+    return fail(C8_ERR_ARG, "c8_krylov: the coarse matrix of the two-level preconditioner is singular or not finite at aggregate " +
+                            std::to_string(bad / NC) + " (coarse row " + std::to_string(bad) + " of " + std::to_string(n) + ")");
+  return fail(C8_ERR_ARG, "c8_krylov: the matrix of level " + std::to_string(nl) + " (the last) of the multilevel preconditioner is singular or not finite at aggregate " +
+                          std::to_string(bad / NC) + " (row " + std::to_string(bad) + " of " + std::to_string(n) + ")");
 }
 
-// e_1 = M_1^-1 r_1 on a list of levels, r_1 and e_1 in the two halves of level 1's vector (of d_kry_cvec when level 1 is the
-// last): down the levels, the dense solve, up again with the sweeps of every block level, level 1 included
+// right-hand side and iterate of level k + 1 of a list: the two halves of the level's vector, of d_kry_cvec on the last level
+template <int NC>
+inline double* level_rhs(c8_ctx const* c, std::vector<c8_kry_level> const& lv, int k) { return k + 1 == (int)lv.size() ? c->d_kry_cvec : lv[k].d_vec; }
+template <int NC>
+inline double* level_x(c8_ctx const* c, std::vector<c8_kry_level> const& lv, int k) {
+  return k + 1 == (int)lv.size() ? c->d_kry_cvec + ((lv[k].n * NC + 1) & ~1) : lv[k].d_vec + (size_t)lv[k].n * NC;
+}
+
+// e_1 = M_1^-1 r_1 on a list of levels, r_1 and e_1 in level_rhs(0) and level_x(0): down the levels, the dense solve, up
+// again with the sweeps of every block level, level 1 included.  The dense solve forms the rows [row0, row0 + nrows) of the
+// last level's e: all of them, or -- over parts with level 1 the last level -- the rows of the rank's own aggregates.
 template <int ND, int NRES>
-hipError_t launch_level_cycle(c8_ctx const* c, std::vector<c8_kry_level> const& lv, KryScalars const* S) {
+hipError_t launch_level_cycle(c8_ctx const* c, std::vector<c8_kry_level> const& lv, int row0, int nrows, KryScalars const* S) {
   constexpr int NC = CoarseDims<ND, NRES>::NC;
   int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1, wpb = TPB / 64;
   hipStream_t const st = c->stream;
-  auto rhs_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec : lv[k].d_vec; };  // of level k + 1
-  auto x_of = [&](int k) { return k + 1 == nl ? c->d_kry_cvec + lda : lv[k].d_vec + (size_t)lv[k].n * NC; };
+  auto rhs_of = [&](int k) { return level_rhs<NC>(c, lv, k); };
+  auto x_of = [&](int k) { return level_x<NC>(c, lv, k); };
   for (int k = 0; k + 1 < nl; ++k)
     hipLaunchKernelGGL((k_level_restrict<ND, NRES>), dim3((lv[k].nagg + wpb - 1) / wpb), dim3(TPB), 0, st, lv[k].nagg, level_agg_tables(lv[k]), rhs_of(k),
                        rhs_of(k + 1), S);
-  hipLaunchKernelGGL(k_coarse_apply, dim3((n + wpb - 1) / wpb), dim3(TPB), 0, st, n, lda, c->d_kry_Ac, rhs_of(nl - 1), x_of(nl - 1), S);
+  if (nrows > 0)
+    hipLaunchKernelGGL(k_coarse_apply, dim3((nrows + wpb - 1) / wpb), dim3(TPB), 0, st, row0, nrows, lda, c->d_kry_Ac, rhs_of(nl - 1), x_of(nl - 1), S);
   for (int k = nl - 2; k >= 0; --k) {
     c8_kry_level const& L = lv[k];
     hipLaunchKernelGGL((k_level_prolong<ND, NRES>), dim3((L.n + TPB - 1) / TPB), dim3(TPB), 0, st, L.n, level_agg_tables(L), x_of(k + 1), x_of(k), S);
@@ -510,20 +538,54 @@ hipError_t launch_level_cycle(c8_ctx const* c, std::vector<c8_kry_level> const& 
   return hipGetLastError();
 }
 
-// x = P_0 M_1^-1 P_0^T rhs: k_restrict, the cycle over the levels, k_prolong; the caller's sweeps on level 0 start from
-// this x
+// x = P_0 M_1^-1 P_0^T rhs on the levels of q: k_restrict, the cycle over the levels, k_prolong; the caller's sweeps on
+// level 0 start from this x
 template <int ND, int NRES>
-hipError_t launch_multilevel(Solve const& q, double const* rhs, double* x) {
+hipError_t levels_apply(Solve const& q, double const* rhs, double* x) {
   constexpr int NC = CoarseDims<ND, NRES>::NC;
   c8_ctx const* c = q.c;
-  std::vector<c8_kry_level> const& lv = c->kry_levels;
-  int const nl = (int)lv.size(), n = lv.back().n * NC, lda = (n + 1) & ~1, wpb = TPB / 64;
+  std::vector<c8_kry_level> const& lv = *q.lv;
+  Level0 const& l0 = q.l0;
+  int const wpb = TPB / 64;
   hipStream_t const st = c->stream;
-  double* const r1 = nl == 1 ? c->d_kry_cvec : lv[0].d_vec;
-  double const* const e1 = nl == 1 ? c->d_kry_cvec + lda : lv[0].d_vec + (size_t)lv[0].n * NC;
-  hipLaunchKernelGGL((k_restrict<ND, NRES>), dim3((c->kry_nagg + wpb - 1) / wpb), dim3(TPB), 0, st, c->kry_nagg, agg_tables(c), q.nn, rhs, r1, q.S);
-  hipError_t const err = launch_level_cycle<ND, NRES>(c, lv, q.S);
+  hipLaunchKernelGGL((k_restrict<ND, NRES>), dim3((l0.total + wpb - 1) / wpb), dim3(TPB), 0, st, l0.total, l0.base, l0.nagg, l0.T, q.nn, rhs,
+                     level_rhs<NC>(c, lv, 0), q.S);
+  hipError_t const err = launch_level_cycle<ND, NRES>(c, lv, 0, lv.back().n * NC, q.S);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL((k_prolong<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, q.nn, q.nb_node, agg_tables(c), e1, x, q.S);
+  hipLaunchKernelGGL((k_prolong<ND, NRES>), dim3(xcd_grid(q.nb_node)), dim3(TPB), 0, st, l0.nown, q.nn, q.nb_node, l0.T, level_x<NC>(c, lv, 0), x, q.S);
   return hipGetLastError();
+}
+
+// what c8_krylov_level_matrix refuses of a list: a level that is not there, a dense copy above the cap
+inline int level_matrix_refusals(std::vector<c8_kry_level> const& lv, int level, int nc) {
+  int const nl = (int)lv.size();
+  if (level < 1 || level > nl)
+    return fail(C8_ERR_ARG, "c8_krylov_level_matrix: level " + std::to_string(level) + " is not one of the levels 1 .. " + std::to_string(nl));
+  long long const nlong = (long long)lv[level - 1].n * nc;
+  if (nlong > COARSE_CAP)
+    return fail(C8_ERR_UNSUPPORTED, "c8_krylov_level_matrix: level " + std::to_string(level) + " has " + std::to_string(nlong) +
+                                    " unknowns: a dense copy is refused above the cap of " + std::to_string(COARSE_CAP));
+  return C8_OK;
+}
+
+// the dense copy of level `level` of a list on the host, after a set-up up to that level (the copy itself is the caller's:
+// C8_HIP, or the notes of Parts): the last level from d_kry_Ac by rows, a block-sparse one spread from its blocks
+inline hipError_t level_copy_start(c8_ctx const* c, std::vector<c8_kry_level> const& lv, int level, int nc, double* out_host, std::vector<double>* blocks) {
+  c8_kry_level const& L = lv[level - 1];
+  int const n = L.n * nc, lda = (n + 1) & ~1;
+  if (level == (int)lv.size())
+    return hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), c->d_kry_Ac, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), n,
+                            hipMemcpyDeviceToHost, c->stream);
+  blocks->resize(L.ga.size() * nc * nc);
+  return hipMemcpyAsync(blocks->data(), L.d_A, blocks->size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+}
+inline void level_copy_finish(std::vector<c8_kry_level> const& lv, int level, int nc, double* out_host, std::vector<double> const& blocks) {
+  if (level == (int)lv.size()) return;
+  c8_kry_level const& L = lv[level - 1];
+  size_t const n = (size_t)L.n * nc;
+  std::fill(out_host, out_host + n * n, 0.);
+  for (int i = 0; i < L.n; ++i)
+    for (int32_t e = L.gp[i]; e < L.gp[i + 1]; ++e)
+      for (int r = 0; r < nc; ++r)
+        for (int k = 0; k < nc; ++k) out_host[((size_t)i * nc + r) * n + (size_t)L.ga[e] * nc + k] = blocks[((size_t)e * nc + r) * nc + k];
 }
