@@ -148,9 +148,12 @@ extern "C" {
 
 int c8_apply_dirichlet(c8_ctx* c, int n, const c8_dbc* dbcs, const double* const x[2], const c8_system* sys, int is_adjoint) {
   if (!c || n < 0 || (n > 0 && !dbcs) || !x || !sys) return c8_fail(C8_ERR_ARG, "c8_apply_dirichlet: null argument");
-  for (int q = 0; q < n; ++q) {  // in deck order: later conditions overwrite earlier ones on shared rows
+  for (int q = 0; q < n; ++q) {  // every condition is checked before the first one is applied: a refused call leaves the system as it was
     c8_dbc const& d = dbcs[q];
     if (d.resid < 0 || d.resid >= c->nres || d.eq < 0 || d.eq >= neq_of(d.resid, c->ndims)) return c8_fail(C8_ERR_ARG, "c8_apply_dirichlet: bad residual/equation index");
+  }
+  for (int q = 0; q < n; ++q) {  // in deck order: later conditions overwrite earlier ones on shared rows
+    c8_dbc const& d = dbcs[q];
     if (d.n <= 0) continue;
     hipLaunchKernelGGL(k_dirichlet, dim3(grid_of(d.n)), dim3(TPB), 0, c->stream, d.n, d.resid, d.eq, d.nodes, d.values,
                        x[d.resid], c->d_nodeptr, c->d_nodeadj, sys->A[d.resid][0], sys->A[d.resid][1], sys->b[d.resid], is_adjoint,
@@ -163,10 +166,13 @@ int c8_apply_dirichlet(c8_ctx* c, int n, const c8_dbc* dbcs, const double* const
 int c8_apply_traction(c8_ctx* c, int n, const c8_tbc* tbcs, const c8_system* sys) {
   if (!c || n < 0 || (n > 0 && !tbcs) || !sys) return c8_fail(C8_ERR_ARG, "c8_apply_traction: null argument");
 
-  for (int q = 0; q < n; ++q) {
+  for (int q = 0; q < n; ++q) {  // checked before the first condition is applied, as in c8_apply_dirichlet
     c8_tbc const& t = tbcs[q];
     bool const side_ok = c->ndims == 2 ? t.nodes_per_face == 2 : (t.nodes_per_face == 3 || t.nodes_per_face == 4);
     if (t.resid != 0 || !side_ok) return c8_fail(C8_ERR_ARG, "c8_apply_traction: tractions act on residual 0 over the sides of the mesh (edges of a 2-D mesh, tri3 / quad4 faces of a 3-D mesh)");
+  }
+  for (int q = 0; q < n; ++q) {
+    c8_tbc const& t = tbcs[q];
     if (t.n <= 0) continue;
     hipLaunchKernelGGL(k_traction, dim3(grid_of(t.n)), dim3(TPB), 0, c->stream, t.n, t.nodes_per_face, t.faces, t.traction,
                        c->d_coords, sys->b[0]);

@@ -323,7 +323,9 @@ typedef struct {
   const double* traction;  /* [n][points][3], points = 1 (edge, tri3) or 4 (quad4); on a 2-D mesh the third entry is ignored */
 } c8_tbc;
 /* apply_primal_dbcs (dbcs.cpp:28-121): for every constrained row keep the diagonal entry, zero the rest
- * of the row in every block, b[row] = diag * (x[row] - value), or 0 when is_adjoint. */
+ * of the row in every block, b[row] = diag * (x[row] - value), or 0 when is_adjoint.  Conditions apply in list order
+ * (the later one wins on a shared row).  Both calls check every condition before they apply the first: after
+ * C8_ERR_ARG the system is as it was. */
 int c8_apply_dirichlet(c8_ctx* ctx, int n, const c8_dbc* dbcs, const double* const x[2], const c8_system* sys, int is_adjoint);
 /* apply_primal_tbcs (tbcs.cpp:88-98): b[row(node, d)] -= T_d N_node w dv over the faces. */
 int c8_apply_traction(c8_ctx* ctx, int n, const c8_tbc* tbcs, const c8_system* sys);

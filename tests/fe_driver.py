@@ -56,7 +56,7 @@ class Dbc:
 
 
 class Tbc:
-    """[resid_idx, list of boundary triangles (node triples), traction(x, y, z, t) -> 3-vector]"""
+    """[resid_idx, list of boundary sides (node pairs, triples or quadruples), traction(x, y, z, t) -> 3-vector]"""
 
     def __init__(self, resid, sides, fn):
         self.resid, self.sides, self.fn = resid, sides, fn
@@ -89,9 +89,23 @@ def apply_dbcs(be, ls, dbcs, x, coords, t, is_adjoint=False):
 
 def apply_tbcs(ls, tbcs, coords, t):
     """tbcs.cpp:17-86 on tri3 boundary faces with the order-1 rule (centroid, N = 1/3); on a 2-D mesh the sides are
-    edges (midpoint, N = 1/2, w dv = length) and a node has two equations."""
+    edges (midpoint, N = 1/2, w dv = length) and a node has two equations; on quad4 faces (the sides of hex8 elements)
+    the 2 x 2 Gauss rule, the traction evaluated at each of the four points (bc_ref.traction_ref in float64).  Sides of
+    any other length are refused."""
     for bc in tbcs:
+        for s in bc.sides:
+            if len(s) not in (2, 3, 4):
+                raise ValueError("apply_tbcs: a side has 2 (edge), 3 (tri3) or 4 (quad4) nodes, not %d" % len(s))
+    for bc in tbcs:
+        quads = [s for s in bc.sides if len(s) == 4]
+        if quads:
+            from bc_ref import face_points_ref, traction_ref
+            pts = face_points_ref(coords, quads, dtype=np.float64)[0]
+            T = np.array([[bc.fn(p[0], p[1], p[2], t) for p in fp] for fp in pts], dtype=np.float64)
+            ls.b[bc.resid] += traction_ref(coords, quads, T, dtype=np.float64)[0]
         for tri in bc.sides:
+            if len(tri) == 4:
+                continue
             if len(tri) == 2:
                 X = coords[list(tri)]
                 length = np.linalg.norm(X[1] - X[0])

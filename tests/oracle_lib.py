@@ -22,11 +22,19 @@ ip = C.POINTER(C.c_int)
 
 
 def build():
+    """Rebuild the oracle when it is missing or older than its source.  One process at a time (a lock on the oracle's
+    directory): the workers of a multi-process test call this side by side, and the second one finds the library built."""
+    import fcntl
     src = os.path.join(ORACLE_DIR, "c8_oracle.cpp")
-    if (not os.path.exists(LIB_PATH)) or (
-        os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(LIB_PATH)
-    ):
-        subprocess.check_call(["make", "-C", ORACLE_DIR, "-s"])
+    fd = os.open(ORACLE_DIR, os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if (not os.path.exists(LIB_PATH)) or (
+            os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(LIB_PATH)
+        ):
+            subprocess.check_call(["make", "-C", ORACLE_DIR, "-s"])
+    finally:
+        os.close(fd)
     return LIB_PATH
 
 
