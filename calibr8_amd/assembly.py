@@ -316,6 +316,18 @@ class Assembler:
         return self._rc(self.L.c8_param_gradient(self.h, C.byref(st), z, C.c_void_p(phi.data_ptr()),
                                                  C.c_void_p(grad.data_ptr())))
 
+    def cauchy(self, u, p, u_prev, p_prev, xi_prev, xi, out=None):
+        """eval_cauchy: the Cauchy stress of the local model at every local-state point, from the stored state:
+        [nelems, npts, 3, 3] float64 on the device (entries outside the ndims x ndims block are 0).  `out`, if given, is
+        overwritten and returned."""
+        torch = self.torch
+        if out is None:
+            out = torch.empty(self.nelems, self.npts, 3, 3, dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and out.numel() == self.nelems * self.npts * 9
+        st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
+        self._rc(self.L.c8_eval_cauchy(self.h, C.byref(st), C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- virtual fields method (one-residual systems; calibr8_amd.vfm.VFMProblem drives these) ----------------------
     def vfm_set_virtual_field(self, w):
         """nodal virtual field [nnodes * ndims] (device tensor, kept by reference)"""

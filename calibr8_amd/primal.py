@@ -266,6 +266,16 @@ class PrimalDriver:
             self.solve_at_step(s)
         return self
 
+    def cauchy(self, step):
+        """eval_cauchy(state, step) from the stored history: the stress field [nelems, npts, 3, 3] of a solved step on the
+        device; zeros for step 0, as in the reference (evaluations.cpp:1687)."""
+        asm = self.asm
+        if not 0 <= step < len(self.u):
+            raise IndexError("step %d has not been solved" % step)
+        if step == 0:
+            return self.torch.zeros(asm.nelems, asm.npts, 3, 3, dtype=self.torch.float64, device=asm.device)
+        return asm.cauchy(self.u[step], self.p[step], self.u[step - 1], self.p[step - 1], self.xi[step - 1], self.xi[step])
+
     def set_measured(self, u_meas, loads):
         """Calibration objective: measured displacements (device tensors) and loads per step, index 0 unused."""
         self.measured = (u_meas, loads)

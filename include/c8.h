@@ -283,6 +283,17 @@ int c8_solve_adjoint_local(c8_ctx* ctx, const c8_state* st, const double* const 
 int c8_param_gradient(c8_ctx* ctx, const c8_state* st, const double* const z[2], const double* phi, double* grad);
 /* eval_qoi (evaluations.cpp:662-756), "average displacement" (avg_disp.cpp:16-33): *J += value. */
 int c8_eval_qoi(c8_ctx* ctx, const c8_state* st, double* J);
+/* eval_cauchy (evaluations.cpp:1659-1748): sigma [num_elems][c8_num_local_points][3][3], DEVICE, OVERWRITTEN.
+ * Row-major; entries with a row or column index >= c8_num_dims() are 0, as in the reference's apf::Matrix3x3.
+ * The local model's cauchy() at every local-state point (ip set 0), from the stored state st->xi of that point and
+ * st->x interpolated there: no local solve, nothing is written but sigma.  Parameters are those of the element's
+ * element set.  The finite-deformation models also gather st->x_prev[0]; under mechanics_plane_stress x[1] and
+ * x_prev[1] are not read.  The reference returns a zero field for step 0; this call always evaluates (the caller
+ * knows its step: calibr8_amd.PrimalDriver.cauchy).  Stream, async mode and return value as c8_assemble_residual
+ * (nothing here can fail a local solve).  Not collective: on a part of a multi-part mesh the ghost and phantom
+ * entries of x must have been imported (c8_halo_scatter_x), as for every other entry point; sigma covers the part's
+ * own elements.  hybrid_hyper_J2_plane_stress needs its embedded network set, as the assembly entry points do. */
+int c8_eval_cauchy(c8_ctx* ctx, const c8_state* st, double* sigma);
 
 /* ---- virtual fields method (VFM): the local constitutive update driven by MEASURED displacements, the internal-force
  * residual contracted with a fixed nodal virtual field w; no global linear solve (virtual_power.cpp).  One-residual
