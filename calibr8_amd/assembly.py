@@ -102,6 +102,8 @@ class Assembler:
         self.ndofs = (self.ndims + (1 if self.nres == 2 else 0)) * self.nn
         self.nnz = [[int(self.L.c8_graph_nnz(h, i, j)) for j in range(2)] for i in range(2)]
         self._graph = None
+        self.kernel = "auto"            # what set_kernel asked for last
+        self.objective = ("avg_disp",)  # ... and set_qoi_avg_disp / set_qoi_calibration: what two contexts must share
         if scatter is not None:  # None: the library's default (staged assembly, see c8_set_scatter_mode)
             self.set_scatter(scatter)
         self.use_current_stream()
@@ -254,6 +256,7 @@ class Assembler:
         iterated, automatically differentiated local solve also where a model has a closed form)"""
         v = {"auto": _l.C8_KERNEL_AUTO, "slot": _l.C8_KERNEL_SLOT, "wave": _l.C8_KERNEL_WAVE, "wave_ad": _l.C8_KERNEL_WAVE_AD, "node": _l.C8_KERNEL_NODE}[variant]
         _l.check(self.L.c8_set_kernel_variant(self.h, v))
+        self.kernel = variant
 
     def set_async(self, flag):
         _l.check(self.L.c8_set_async(self.h, int(flag)))
@@ -328,6 +331,23 @@ class Assembler:
         self._rc(self.L.c8_eval_cauchy(self.h, C.byref(st), C.c_void_p(out.data_ptr())))
         return out
 
+    def error_contributions(self, u, p, u_prev, p_prev, xi_prev, xi, z_u, z_p, phi, E_R=None, E_C=None):
+        """eval_error_contributions: (E_R, E_C), [nelems] float64 on the device: E_R[e] += z_e . R_e, E_C[e] += sum_pt phi_pt .
+        C_pt at the stored state.  Allocated as zeros when not given, accumulated into when given."""
+        torch = self.torch
+        if E_R is None:
+            E_R = torch.zeros(self.nelems, dtype=torch.float64, device=self.device)
+        if E_C is None:
+            E_C = torch.zeros(self.nelems, dtype=torch.float64, device=self.device)
+        for t in (z_u, z_p, phi, E_R, E_C):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        assert E_R.numel() == self.nelems and E_C.numel() == self.nelems and phi.numel() == self.nelems * self.npts * self.nloc
+        st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
+        z = (C.c_void_p * 2)(z_u.data_ptr(), z_p.data_ptr())
+        self._rc(self.L.c8_eval_error_contributions(self.h, C.byref(st), z, C.c_void_p(phi.data_ptr()),
+                                                    C.c_void_p(E_R.data_ptr()), C.c_void_p(E_C.data_ptr())))
+        return E_R, E_C
+
     # ---- virtual fields method (one-residual systems; calibr8_amd.vfm.VFMProblem drives these) ----------------------
     def vfm_set_virtual_field(self, w):
         """nodal virtual field [nnodes * ndims] (device tensor, kept by reference)"""
@@ -382,6 +402,7 @@ class Assembler:
     # ---- objective ----
     def set_qoi_avg_disp(self):
         _l.check(self.L.c8_set_qoi_avg_disp(self.h))
+        self.objective = ("avg_disp",)
 
     def set_qoi_calibration(self, faces, weights=(1.0, 1.0, 1.0), balance=1.0, coord_idx=1, coord_value=0.0,
                             coord_tol=1e-8, comp=1, dt_over_T=1.0):
@@ -397,6 +418,8 @@ class Assembler:
         d.balance_factor, d.coord_idx, d.coord_value, d.coord_tol = float(balance), int(coord_idx), float(coord_value), float(coord_tol)
         d.reaction_comp, d.dt_over_total_time = int(comp), float(dt_over_T)
         _l.check(self.L.c8_set_qoi_calibration(self.h, C.byref(d)))
+        self.objective = ("calibration", f.tobytes(), f.shape, tuple(float(w) for w in weights), float(balance), int(coord_idx),
+                          float(coord_value), float(coord_tol), int(comp), float(dt_over_T))
 
     def set_allreduce(self, dist, num_parts):
         """Multi-part objective sums: `dist` = an initialised torch.distributed module (SUM all-reduce of host doubles)."""

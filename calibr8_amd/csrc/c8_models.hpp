@@ -1215,7 +1215,9 @@ C8_HD void nn_value_slope(double const* nn, double x, double* w, double& y, doub
 #ifndef C8_BLOCK
 #define C8_BLOCK 64
 #endif
-#if defined(__HIP_DEVICE_COMPILE__)
+// (a translation unit whose lanes do not form such groups defines C8_NN_WORK itself before this header: c8_error.hip)
+#if defined(C8_NN_WORK)
+#elif defined(__HIP_DEVICE_COMPILE__)
 #define C8_NN_WORK(name)                                                        \
   __shared__ double name##_all[(C8_BLOCK + 5) / 6][4 * NN_MAX_WIDTH];          \
   double* const name = name##_all[threadIdx.x / 6]

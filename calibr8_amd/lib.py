@@ -169,6 +169,7 @@ SYMBOLS = [
     ("c8_param_gradient", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     ("c8_eval_qoi", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p]),
     ("c8_eval_cauchy", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p]),
+    ("c8_eval_error_contributions", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_vfm_set_virtual_field", C.c_int, [C.c_void_p, C.c_void_p]),
     ("c8_vfm_internal_power", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p]),
     ("c8_vfm_forward_sens", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

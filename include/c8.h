@@ -294,6 +294,28 @@ int c8_eval_qoi(c8_ctx* ctx, const c8_state* st, double* J);
  * entries of x must have been imported (c8_halo_scatter_x), as for every other entry point; sigma covers the part's
  * own elements.  hybrid_hyper_J2_plane_stress needs its embedded network set, as the assembly entry points do. */
 int c8_eval_cauchy(c8_ctx* ctx, const c8_state* st, double* sigma);
+/* eval_error_contributions (evaluations.cpp:930-1073): the adjoint-weighted residuals that localise the error estimate
+ * of the objective, two numbers per element, both ACCUMULATED INTO (the caller sums its steps into one pair of fields):
+ *   E_R[e] += z_e . R_e(x)          R the context's global residual, the integrand c8_assemble_residual scatters: per
+ *                                   point of ip set 0  w dv (Gu : grad z_u + Vp z_p + Gp . grad z_p)  with z interpolated by
+ *                                   the element's shape functions, plus  w dv flux_pressure z_p  on ip set 1 (`mechanics`);
+ *   E_C[e] += sum_pt phi_pt . C     C the local model's residual at (st->x interpolated, st->xi, st->xi_prev), on the
+ *                                   branch the model itself chooses (the reference's force_path is not supported);
+ *                                   `elastic` contributes nothing.
+ * Evaluated at the STORED state: no local solve, no AD, nothing is written but E_R and E_C [num_elems].  z as in
+ * c8_solve_adjoint_local (z[1] is not read when c8_num_residuals() == 1), phi [elems][c8_num_local_points]
+ * [c8_num_local_dofs]; DEVICE pointers.  The reference also scatters R into b (:1030); callers get that from
+ * c8_assemble_residual.  No floating-point atomics: every element's two sums are formed in a fixed order (ip set 0
+ * ascending, then ip set 1), the same inputs give the same bytes.  Stream, async mode and return value as
+ * c8_assemble_residual (nothing here can fail a local solve).  Not collective: on a part of a multi-part mesh the ghost
+ * and phantom entries of x and z must have been imported; the outputs cover the part's own elements, each of which
+ * belongs to exactly one part.  hybrid_hyper_J2_plane_stress needs its embedded network set.
+ * Model-form error (calibr8_amd.model_form_error): z and phi come from c8_adjoint_solve_step on a context of the richer
+ * model, linearised about the state of the cheaper one.  Under C8_KERNEL_AUTO the row-per-node adjoint kernels (small_J2 on
+ * hex8) recompute the local state from xi_prev and never read st->xi -- for such a prolonged state the wrong linearisation
+ * point -- so a context used that way must be put on C8_KERNEL_WAVE_AD (c8_set_kernel_variant) first. */
+int c8_eval_error_contributions(c8_ctx* ctx, const c8_state* st, const double* const z[2], const double* phi, double* E_R,
+                                double* E_C);
 
 /* ---- virtual fields method (VFM): the local constitutive update driven by MEASURED displacements, the internal-force
  * residual contracted with a fixed nodal virtual field w; no global linear solve (virtual_power.cpp).  One-residual
