@@ -13,12 +13,13 @@
 // the shape functions -- the bulk of the arithmetic -- is split over the nodes without redundancy: every 4 x 4
 // block of the element matrix is formed exactly once, by the wavefront of its row node.
 //
-//   top      lane = (point, node)   forward assembly: the 64 shape values of the reference element at its points into LDS
-//            (nshape): they are the same for every element, phases A and B read them instead of forming them at every step
+//   top      lane = pattern         forward assembly: the eight shape values of the reference element at its points into LDS
+//            (nshape, hex_pattern): phase B and the row node read them instead of forming them at every step
 //   phase A  lane = (element s of the node, point)      interpolate the point quantities from the element's nodal
-//            values and cached shape tables, closed form (radial return, consistent tangent), the row node's record of
-//            the point into LDS, the point's share of the node's residual; the lane of the element's local node 0
-//            stores the converged local state
+//            values -- their gradients in the reference element first, then the point's cached inverse Jacobian (nine
+//            coalesced loads) --, closed form (radial return, consistent tangent), the row node's record of the point into
+//            LDS, the point's share of the node's residual; the lane of the element's local node 0 stores the converged
+//            local state
 //   phase B  lane = (element s of the node, column node m)   the 4 x 4 block d R_(node,.) / d x_(m,.) summed over the
 //            element's eight points: 16 accumulators
 //   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order.  The
@@ -26,9 +27,8 @@
 //   phase D  the finished rows added to (or assigned to) the four CSR blocks -- four straight copies, lane j + 64 it
 //            takes entry j + 64 it of a block -- the residual entries to b
 //
-// In the walks over the skewed shape table (phases A and B) a lane keeps ONE rotating byte offset, (off + 8) & 56, and
-// derives every address of a step from it by a shift: the table's two columns, the nodal values, the record, nshape.
-// (With nshape in place this saves 7 vector instructions per node and costs 4 registers: no measurable time either way.)
+// In the walk over the skewed shape table (phase B) a lane keeps ONE rotating byte offset, (off + 8) & 56, and derives every
+// address of a step from it by a shift: the table's two columns, the record, nshape.
 //
 // Requires an element with 8 nodes, 8 coupled points and identical point sets for both ip sets (hex8), the cached
 // shape tables (c8_set_shape_cache) and xi != xi_prev (an element's previous state is read by eight wavefronts).
@@ -67,7 +67,7 @@ template <class E, class ModelD, int MAXDEG, bool MANY> struct NodeShared {
   static constexpr int NREC = 8 * E::NP0 * LDR, NACC = MAXDEG * 16;
   alignas(16) double buf[MANY ? NREC + NACC : (NREC > NACC ? NREC : NACC)];
   alignas(16) double nodal[8][E::NN][4];    // (u_0, u_1, u_2, p) of the nodes of the eight elements, loaded one node per lane
-  double nshape[E::NP0][E::NN];             // N_n at point pt of the reference element: HexShape::of_point(pt).at_node(n)
+  double nshape[8];                         // N of the reference element by agreement pattern of node and point (hex_pattern)
                                             // (forward assembly; the struct has no ADJ parameter, the adjoint leaves it unused)
   double el[8][2];                          // per element: the model's per-element scalars (closed_form_row)
   double bsum[4];
@@ -95,14 +95,29 @@ template <int MAXDEG> struct NodeLane {
   bool valid;
 };
 
+// The reference hex8 at its Gauss points BY AGREEMENT PATTERN.  Node signs and point coordinates are +-1 and +-1/sqrt(3) per
+// axis, so N_m and dN_m/dxi at a point depend only on the set j of axes on which the node's sign equals the point's (bit k of
+// j):   N = v[0],   dN/dxi_k = s_k v[1 + k]   with s_k the node's sign along k,
+// operation for operation E::N and E::dNdxi (a change of sign is exact).  hex_code(n) holds node n's sign bits, the point's
+// are pt itself: j = hex_code(n) ^ pt ^ 7.  hex_code is linear over ^ and its own inverse, so the node with pattern j at
+// point pt is hex_code(j) ^ hex_code(pt ^ 7).  With j a compile-time constant the four values are constants.
+C8_HD constexpr int hex_code(int n) { return n ^ ((n >> 1) & 1); }
+template <class E> C8_HD void hex_pattern(int j, double* v) {
+  double c[3], w;
+  E::point(0, 7, c, w);  // (+, +, +)
+  double const a = 1. + ((j & 1) ? c[0] : -c[0]), b = 1. + ((j & 2) ? c[1] : -c[1]), d = 1. + ((j & 4) ? c[2] : -c[2]);
+  v[0] = 0.125 * a * b * d;
+  v[1] = 0.125 * b * d;
+  v[2] = 0.125 * a * d;
+  v[3] = 0.125 * a * b;
+}
+
 // shape values of the reference hex8 at its Gauss points: E::N(n, xi) operation for operation, 0.125 (1 + sx xi_0)
 // (1 + sy xi_1) (1 + sz xi_2), with either the point (of_point) or the node (of_node) fixed per lane and the other index a
 // lane value; signs are selected as values (no indexed tables: they would live in scratch).
-// Forward assembly: evaluated once per wavefront, one (point, node) pair per lane, into NodeShared::nshape.  One table
-// serves the lanes that own a point and walk the nodes (phase A) and those that own a node and walk the points (phase B):
-// the signs are +-1, so 1 + s * xi is exact in the product whichever index is fixed, and the factors are multiplied in the
-// same order -- at_node and at_point give the same bits.  Adjoint assembly: formed at every step as before; with the table
-// K3 measured 2.5-3.4 % SLOWER.
+// Adjoint assembly only (the forward assembly reads NodeShared::nshape): formed at every step; with a table of the values in
+// LDS K3 measured 2.5-3.4 % SLOWER.  The signs are +-1, so 1 + s * xi is exact in the product whichever index
+// is fixed, and the factors are multiplied in the same order -- at_node and at_point give the same bits.
 template <class E> struct HexShape {
   double c[3];  // of_point: the point's coordinates; of_node: the node's signs
   C8_HD static HexShape of_point(int pt) {
@@ -156,11 +171,15 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     }
     if (lane < 4) sh.bsum[lane] = 0.;
   };
-  // forward assembly: the reference element's shape values, lane = (point, node).  Here and not in the kernel's wrapper: the
+  // forward assembly: the reference element's shape values, lane = pattern.  Here and not in the kernel's wrapper: the
   // function is the unit the CPU emulation calls
   if (!ADJ || MANY) {
     ex.each([&](int lane) {
-      if (!ADJ) sh.nshape[lane >> 3][lane & 7] = HexShape<E>::of_point(lane >> 3).at_node(lane & 7);
+      if (!ADJ && lane < 8) {
+        double v[4];
+        hex_pattern<E>(lane, v);
+        sh.nshape[lane] = v[0];
+      }
       if (MANY) zero_acc(lane);
     });
     ex.sync();
@@ -197,9 +216,16 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       if (!r.valid) return;
       int const e = r.e, a = r.a;
       double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
-      double const* const Np = sh.nshape[pt];                  // this point's shape values: forward, from the table;
-      HexShape<E> NpH;                                         // adjoint, formed per step
-      if constexpr (ADJ) NpH = HexShape<E>::of_point(pt);
+      size_t const q0 = ((size_t)e * E::NP0 + pt) * NL;
+      // the point's inverse Jacobian G[3 k + d] = d xi_k / d x_d (the eight lanes of an element read 64 contiguous bytes per
+      // component) and, forward, its previous state: issued ahead of the interpolation, which reads LDS only
+      double G[9], xi_old[NL];
+      C8_UNROLL
+      for (int c = 0; c < 9; ++c) G[c] = t[SHAPE_JINV + 8 * c + pt];
+      if constexpr (!ADJ) {
+        C8_UNROLL
+        for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
+      }
       // adjoint assembly: this point's history entries (f at the node's four rows, g), fetched under the interpolation
       double fh4[4] = {0., 0., 0., 0.}, gx[NL];
       C8_UNROLL
@@ -210,57 +236,53 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
         C8_UNROLL
         for (int j = 0; j < NL; ++j) gx[j] = aa.g[((size_t)e * E::NP0 + pt) * NL + j];
       }
-      // interpolation (global_residual.cpp:289-332).  The table is skewed (shape_dn_offset): at step i the element's eight
-      // lanes read row i, this lane the entry of node m = (i - pt) mod 8 -- the sum over the nodes starts at node -pt mod 8
-      // and wraps; the row node's own entry (g below) is kept when it comes by.  Four nodes' operands in flight at a time.
-      // off = 8 m, the byte offset of node m in a row of eight doubles, rotates from step to step; shifted, it addresses the
-      // row's 16-byte column, its 8-byte column, the node's values in sh.nodal and its shape value
+      // interpolation (global_residual.cpp:289-332): the gradients of u_0, u_1, u_2, p in the REFERENCE element first (R),
+      // then q = R G.  The nodes are taken in the order of their agreement pattern with the point, i = 0 .. 7 -- node
+      // hex_code(i) ^ hex_code(pt ^ 7) --, so the reference values of a step are compile-time constants up to the point's
+      // own signs, which leave the sum and multiply R afterwards: 13 multiply-adds and one 32-byte LDS read per node, no
+      // table.  The row node's own dN_a/dx (g below) is dN_a/dxi G.  (Until this form the phase walked the skewed dN/dx
+      // table, 24 bytes per lane and node: DESIGN 3.8.)
       double q[WQ];
       C8_UNROLL
       for (int c = 0; c < WQ; ++c) q[c] = 0.;
-#ifndef C8_TUNE_NODE_GSEL
-#define C8_TUNE_NODE_GSEL 0
-#endif
-      double g[3] = {0., 0., 0.};
-      int off = ((0 - pt) & 7) * 8;
-      C8_UNROLL
-      for (int i = 0; i < E::NN; ++i) {
-        double const* const row = t + i * 24;
-        double const* const d01 = at_byte(row, 2 * off);
-        double const d0 = d01[0], d1 = d01[1], d2 = *at_byte(row + 16, off);
-        if (C8_TUNE_NODE_GSEL) {
-          bool const own = off == 8 * a;
-          g[0] = own ? d0 : g[0]; g[1] = own ? d1 : g[1]; g[2] = own ? d2 : g[2];
+      double g[3];
+      {
+        double R[12], pN = 0.;
+        C8_UNROLL
+        for (int c = 0; c < 12; ++c) R[c] = 0.;
+        int const mo = hex_code(pt ^ 7) * 32;  // byte offset of a node's four values in sh.nodal[s]
+        C8_UNROLL
+        for (int i = 0; i < E::NN; ++i) {
+          double v[4];
+          hex_pattern<E>(i, v);
+          double const t0 = (i & 1) ? v[1] : -v[1], t1 = (i & 2) ? v[2] : -v[2], t2 = (i & 4) ? v[3] : -v[3];
+          double const* const nv = at_byte(sh.nodal[s][0], mo ^ (hex_code(i) * 32));
+          double const u0 = nv[0], u1 = nv[1], u2 = nv[2], pm = nv[3];
+          R[0] += u0 * t0; R[1] += u0 * t1; R[2] += u0 * t2;
+          R[3] += u1 * t0; R[4] += u1 * t1; R[5] += u1 * t2;
+          R[6] += u2 * t0; R[7] += u2 * t1; R[8] += u2 * t2;
+          pN += pm * v[0];
+          R[9] += pm * t0; R[10] += pm * t1; R[11] += pm * t2;
         }
-        double Nm;
-        if constexpr (ADJ) Nm = NpH.at_node(off >> 3);
-        else Nm = *at_byte(Np, off);
-        double const* const nv = at_byte(sh.nodal[s][0], 4 * off);
-        double const u0 = nv[0], u1 = nv[1], u2 = nv[2], pm = nv[3];
-        off = (off + 8) & 56;
-        q[0] += u0 * d0; q[1] += u0 * d1; q[2] += u0 * d2;
-        q[3] += u1 * d0; q[4] += u1 * d1; q[5] += u1 * d2;
-        q[6] += u2 * d0; q[7] += u2 * d1; q[8] += u2 * d2;
-        q[9] += pm * Nm;
-        q[10] += pm * d0; q[11] += pm * d1; q[12] += pm * d2;
-#ifndef C8_TUNE_NODE_AGROUP
-#define C8_TUNE_NODE_AGROUP 8
-#endif
-#ifndef C8_TUNE_NODE_AGROUP_ADJ
-#define C8_TUNE_NODE_AGROUP_ADJ 2
-#endif
-        // nodes whose operands are in flight together: as measured (forward 8: 4.51 ms, 4: 4.70, 2: 4.57; adjoint 2: 5.39, 4: 5.55, 8: 5.66)
-        if ((i + 1) % (ADJ ? C8_TUNE_NODE_AGROUP_ADJ : C8_TUNE_NODE_AGROUP) == 0) {
+        double const s0 = (pt & 1) ? 1. : -1., s1 = (pt & 2) ? 1. : -1., s2 = (pt & 4) ? 1. : -1.;
+        C8_UNROLL
+        for (int f = 0; f < 4; ++f) {
+          double const r0 = s0 * R[3 * f], r1 = s1 * R[3 * f + 1], r2 = s2 * R[3 * f + 2];
           C8_UNROLL
-          for (int c = 0; c < 13; ++c) C8_PIN(q[c]);
-          C8_SCHED_FENCE();
+          for (int d = 0; d < 3; ++d) q[(f < 3 ? 3 * f : 10) + d] = r0 * G[d] + r1 * G[3 + d] + r2 * G[6 + d];
         }
+        q[9] = pN;
+        double xa[3], wa, da[3];
+        E::point(0, pt, xa, wa);
+        E::dNdxi(a, xa, da);
+        C8_UNROLL
+        for (int d = 0; d < 3; ++d) g[d] = da[0] * G[d] + da[1] * G[3 + d] + da[2] * G[6 + d];
       }
       C8_NSTAMP(7);
-      size_t const q0 = ((size_t)e * E::NP0 + pt) * NL;
-      double xi_old[NL];
-      C8_UNROLL
-      for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
+      if constexpr (ADJ) {
+        C8_UNROLL
+        for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
+      }
       int const es = mt.elem_set ? mt.elem_set[e] : 0;
       typename Model::ClosedForm cf;
       Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, t[SHAPE_H], ms.stab_mult, cf, true);
@@ -270,10 +292,9 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       }
       C8_NSTAMP(8);
       double const w = t[SHAPE_WDV + pt];
-      if (!C8_TUNE_NODE_GSEL) { g[0] = t[shape_dn_offset(pt, a, 0)]; g[1] = t[shape_dn_offset(pt, a, 1)]; g[2] = t[shape_dn_offset(pt, a, 2)]; }
       double Na;
-      if constexpr (ADJ) Na = NpH.at_node(a);
-      else Na = Np[a];
+      if constexpr (ADJ) Na = HexShape<E>::of_point(pt).at_node(a);
+      else Na = sh.nshape[hex_code(a) ^ pt ^ 7];
       double* const rc = sh.rec(s, pt);
       double el[2];
       Model::template closed_form_row<ADJ>(cf.t, w, g, Na, rc, el);
@@ -329,6 +350,7 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       C8_UNROLL
       for (int k = 0; k < AH; ++k) { hq[k][0] = t[k * 24 + m * 2 + 0]; hq[k][1] = t[k * 24 + m * 2 + 1]; hq[k][2] = t[k * 24 + 16 + m]; }
       int off = ((0 - m) & 7) * 8;
+      int const cm8 = (hex_code(m) ^ 7) * 8;  // forward: off ^ cm8 is the byte offset of N_m at point off / 8 in nshape
       C8_UNROLL
       for (int i = 0; i < E::NP0; ++i) {
         hq[AH][0] = hq[AH][1] = hq[AH][2] = 0.;
@@ -340,7 +362,7 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
         double const hc[3] = {hq[0][0], hq[0][1], hq[0][2]};
         double Nm;
         if constexpr (ADJ) Nm = Nn.at_point(off >> 3);
-        else Nm = *at_byte(&sh.nshape[0][m], E::NN * off);
+        else Nm = *at_byte(sh.nshape, off ^ cm8);
         Model::closed_form_block(at_byte(sh.rec(s, 0), SH::LDR * off), el, hc, Nm, r.J);
         off = (off + 8) & 56;
         // one point's record in registers at a time: without the lines below the compiler fetches the records of all
@@ -426,6 +448,9 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
 #endif
     ex.sync();
     C8_NSTAMP(4);
+    // MANY = false is the form for nodes with at most eight elements: one round, said here so that the compiler does not keep
+    // the CSR entries fetched above in registers for a second one (they would be live through phases A and B)
+    if (!MANY) break;
   }
   // ---- phase D: rows out (the tail of gather_node_rows) -------------------------------------------------------------
   ex.each([&](int lane_) {

@@ -35,9 +35,12 @@ constexpr int WQ = 16;   // point quantities: grad_u (0..8 row-major), p (9), gr
 constexpr int WF = 13;   // point fluxes: Gu (0..8 row-major), Vp (9), Gp (10..12)
 
 // ---- cached shape tables (static geometry) --------------------------------------------------------------------
-// Per element: dN[pt][n][3] (lane = pt*8 + n reads its three values contiguously), w dv [pt], element size h.
-constexpr int SHAPE_STRIDE = 208;  // 192 + 8 + 1, padded to a multiple of 64 bytes
-constexpr int SHAPE_WDV = 192, SHAPE_H = 200;
+// Per element: dN[pt][n][3] (lane = pt*8 + n reads its three values contiguously), w dv [pt], element size h, and the
+// inverse Jacobian G[k][d] = d xi_k / d x_d of every point, component-major and point-minor: t[SHAPE_JINV + 8 (3 k + d) + pt],
+// so that dN/dx_d = sum_k dN/dxi_k G[k][d] and the eight lanes of an element (one per point) read 64 contiguous, aligned
+// bytes per component.
+constexpr int SHAPE_STRIDE = 280;  // 192 + 8 + 1, padded to 208 (a multiple of 64 bytes), + 72
+constexpr int SHAPE_WDV = 192, SHAPE_H = 200, SHAPE_JINV = 208;
 // dN/dx of (point pt, node m), component d, within an element's cached table.  The 8 x 8 entries are stored SKEWED: row
 // r = (pt + m) mod 8, column m -- per row first the components 0 and 1 of the eight columns (16 doubles), then their
 // components 2 (8 doubles).  The eight lanes of an element then read ONE row of 192 contiguous bytes per step whether a lane
@@ -51,8 +54,32 @@ template <class E> struct ShapeShared {
   double dN[E::NP0][E::NN][3];
   double wdv[E::NP0];
   double h;
+  double G[E::NP0][9];  // d xi_k / d x_d at the point, [3 k + d]
 };
 struct ShapeLane {};
+// the inverse Jacobian of point pt, the arithmetic of shape_entry (which keeps only its products with dN/dxi)
+template <class E, class SH> C8_HD void shape_jinv(SH const& sh, int pt, double* G) {
+  double xi[3], w;
+  E::point(0, pt, xi, w);
+  double J[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};
+  C8_UNROLL
+  for (int n = 0; n < E::NN; ++n) {
+    double g[3];
+    E::dNdxi(n, xi, g);
+    C8_UNROLL
+    for (int a = 0; a < 3; ++a)
+      C8_UNROLL
+      for (int b = 0; b < 3; ++b) J[a][b] += g[a] * sh.X[n][b];
+  }
+  Tens3<double> Jt;
+  Jt.xx = J[0][0]; Jt.xy = J[0][1]; Jt.xz = J[0][2];
+  Jt.yx = J[1][0]; Jt.yy = J[1][1]; Jt.yz = J[1][2];
+  Jt.zx = J[2][0]; Jt.zy = J[2][1]; Jt.zz = J[2][2];
+  Tens3<double> const Ji = inverse(Jt);  // Ji(d, k) = d xi_k / d x_d
+  G[0] = Ji.xx; G[1] = Ji.yx; G[2] = Ji.zx;
+  G[3] = Ji.xy; G[4] = Ji.yy; G[5] = Ji.zy;
+  G[6] = Ji.xz; G[7] = Ji.yz; G[8] = Ji.zz;
+}
 // one wavefront per element, the arithmetic of the kernels' own shape phase (shape_entry, elem_size)
 template <class E, class EX> C8_HD void store_shape_tables(EX& ex, ShapeShared<E>& sh, MeshTables const& mt, double* tab, int e) {
   static_assert(E::NN == 8 && E::NP0 == 8, "hex8-like element");
@@ -66,6 +93,7 @@ template <class E, class EX> C8_HD void store_shape_tables(EX& ex, ShapeShared<E
   ex.each([&](int lane) {
     shape_entry<E>(sh, 0, lane >> 3, lane & 7, (lane & 7) + 1);
     if (lane == 0) sh.h = elem_size<E>(sh);
+    if ((lane & 7) == 1) shape_jinv<E>(sh, lane >> 3, sh.G[lane >> 3]);
   });
   ex.sync();
   ex.each([&](int lane) {
@@ -76,7 +104,9 @@ template <class E, class EX> C8_HD void store_shape_tables(EX& ex, ShapeShared<E
     t[shape_dn_offset(pt, n, 2)] = sh.dN[pt][n][2];
     if (lane < E::NP0) t[SHAPE_WDV + lane] = sh.wdv[lane];
     if (lane == E::NP0) t[SHAPE_H] = sh.h;
-    if (lane > E::NP0 && lane < SHAPE_STRIDE - SHAPE_H + E::NP0) t[SHAPE_H + lane - E::NP0] = 0.;  // padding
+    if (lane > E::NP0 && lane < SHAPE_JINV - SHAPE_H + E::NP0) t[SHAPE_H + lane - E::NP0] = 0.;  // padding
+    C8_UNROLL
+    for (int q = lane; q < 9 * E::NP0; q += 64) t[SHAPE_JINV + q] = sh.G[q & 7][q >> 3];
   });
   ex.sync();
 }

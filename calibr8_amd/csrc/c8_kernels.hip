@@ -462,8 +462,10 @@ template <class E> static hipError_t launch_gather_rows(GatherArgs const& ga, in
 // Measured on the 100^3 brick (K1 ms / K3 ms / HBM-side GB per assembly with FETCH_SIZE doubled): stripes of 64: 4.37 / 5.20 /
 // 16.9; 256: 4.33 / 5.12 / 13.9; 512: 4.36 / 5.21 / 13.0; 1024: 4.36 / 5.30 / 12.5; 2048: 4.36 / 5.28 / 12.3; 16384 and one
 // contiguous eighth of the nodes per XCD: 4.71 / - / 12.1 (profiles/README.md, round 3).  Those are the figures of the kernel
-// before its index and shape-value bookkeeping was stripped (last part); with stripes of 256 the present kernels
-// take 4.22 / 5.11-5.14 ms beside 4.40 / 5.15-5.17 ms of their predecessors in one call (profiles/README.md, node_image_*).
+// before its index and shape-value bookkeeping was stripped; with stripes of 256 the kernels without that
+// bookkeeping took 4.22 / 5.11-5.14 ms beside 4.40 / 5.15-5.17 ms of their predecessors in one call (profiles/README.md,
+// node_image_*).  The present kernels take phase A's gradients from the cached inverse Jacobian instead of the dN/dx table:
+// 3.68 / 4.51 ms beside 4.18 / 5.21 ms of those in one call (last part; profiles/README.md, jinv_*).
 #ifndef C8_NODE_WAVES
 #define C8_NODE_WAVES 3
 #endif
