@@ -3583,4 +3583,29 @@ double c8o_shape(int elem_type, double const* X, double const* xi3, double* N, d
   return dv;
 }
 
+// eig_spd_cos (what = 0) and polar_rotation (what = 1) on their own, one tangent direction per case: in / din are the
+// nine entries of the tensor and of its tangent in row order.  eig_spd_cos writes V to out[0..8] and the eigenvalues to
+// out[9..11], polar_rotation writes R to out[0..8]; dout has the tangents.  A case takes 9 inputs and 12 outputs.
+// tests/math_cases.py sets the constants of its error bars from these.
+int c8o_tensor_probe(int what, double const* in, double const* din, int n_cases, double* out, double* dout) {
+  if (what != 0 && what != 1) return -1;
+  for (int c = 0; c < n_cases; ++c) {
+    Tens<Fad> A;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+      A(i, j).v = in[c * 9 + i * 3 + j];
+      A(i, j).n = 1;
+      A(i, j).d[0] = din[c * 9 + i * 3 + j];
+    }
+    Tens<Fad> V, D;
+    if (what == 0) eig_spd_cos(A, V, D);
+    else V = polar_rotation(A);
+    for (int k = 0; k < 12; ++k) {
+      Fad const& x = k < 9 ? V(k / 3, k % 3) : D(k - 9, k - 9);
+      out[c * 12 + k] = (what == 1 && k >= 9) ? 0. : x.v;
+      dout[c * 12 + k] = (what == 1 && k >= 9) ? 0. : x.dx(0);
+    }
+  }
+  return 0;
+}
+
 }  // extern "C"

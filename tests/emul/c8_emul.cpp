@@ -18,6 +18,7 @@
 #include "../../calibr8_amd/csrc/c8_host.hpp"
 #include "../../calibr8_amd/csrc/c8_qoi_host.hpp"
 #include "../../calibr8_amd/csrc/c8_registry.hpp"
+#include "../math_ops.hpp"
 
 using namespace c8;
 
@@ -502,3 +503,13 @@ extern "C" int c8emu_dual_op(int op, double a, double da, double b, double db, d
   return 0;
 }
 
+
+// The whole of c8_math.hpp by operation number, for tests/test_dual_math_edges.py: the table of tests/math_ops.hpp (the
+// device harness tests/math_device compiles the same one) on n_cases cases of 18 inputs and 21 outputs each
+extern "C" int c8emu_math_op(int op, double const* in, double const* din, int n_cases, double* out, double* dout) {
+  for (int c = 0; c < n_cases; ++c) {
+    size_t const i = (size_t)c * c8_math_ops::MO_NIN, o = (size_t)c * c8_math_ops::MO_NOUT;
+    if (c8_math_ops::math_op(op, in + i, din + i, out + o, dout + o) < 0) return -1;
+  }
+  return 0;
+}
