@@ -10,4 +10,4 @@ from .assembly import Assembler, LinearSystem, brick_mesh, brick_partition  # no
 from .primal import PrimalDriver, adjoint_gradient, device_solver, distributed_device_solver, scipy_solver  # noqa: F401
 from .inverse import FEMUProblem, InverseProblem, lbfgs_minimize  # noqa: F401
 from .vfm import VFMProblem  # noqa: F401
-from .error import ModelFormError, model_form_error  # noqa: F401
+from .error import ModelFormError, ModelFormErrorVerify, model_form_error, model_form_error_verify  # noqa: F401

@@ -74,6 +74,7 @@ class Assembler:
         self.elem_type = int(elem_type)
         self.nnodes, self.nelems, self.nn = self.coords.shape[0], self.conn.shape[0], self.conn.shape[1]
         self.local_type = local_type
+        self.local_abs_tol = float(abs_tol)  # of the local Newton iteration: |C|_2 of a converged point is below it
         self.params = np.ascontiguousarray(np.atleast_2d(np.asarray(params, dtype=np.float64)))
         self.nsets = self.params.shape[0]
         self._es = None if elem_set is None else np.ascontiguousarray(elem_set, dtype=np.int32)
@@ -347,6 +348,33 @@ class Assembler:
         self._rc(self.L.c8_eval_error_contributions(self.h, C.byref(st), z, C.c_void_p(phi.data_ptr()),
                                                     C.c_void_p(E_R.data_ptr()), C.c_void_p(E_C.data_ptr())))
         return E_R, E_C
+
+    def _exact(self, fn, state, fine, z_u, z_p, phi, E_R, E_C):
+        torch = self.torch
+        if E_R is None:
+            E_R = torch.zeros(self.nelems, dtype=torch.float64, device=self.device)
+        if E_C is None:
+            E_C = torch.zeros(self.nelems, dtype=torch.float64, device=self.device)
+        for t in (z_u, z_p, phi, E_R, E_C):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        assert E_R.numel() == self.nelems and E_C.numel() == self.nelems and phi.numel() == self.nelems * self.npts * self.nloc
+        st, sf = self._state(*state), self._state(*fine)
+        z = (C.c_void_p * 2)(z_u.data_ptr(), z_p.data_ptr())
+        self._rc(fn(self.h, C.byref(st), C.byref(sf), z, C.c_void_p(phi.data_ptr()), C.c_void_p(E_R.data_ptr()),
+                    C.c_void_p(E_C.data_ptr())))
+        return E_R, E_C
+
+    def exact_errors(self, state, fine, z_u, z_p, phi, E_R=None, E_C=None):
+        """eval_exact_errors: (E_R, E_C), [nelems] float64 on the device, the derivative of the error contributions along
+        fine - state:  E_R[e] += -z_e . (dR/dx dx + dR/dxi dxi),  E_C[e] += -sum_pt phi_pt . (dC/dx dx + dC/dxi dxi + dC/dx_prev
+        dx_prev + dC/dxi_prev dxi_prev).  `state` and `fine` are (u, p, u_prev, p_prev, xi_prev, xi) device tensors; nothing
+        of `fine` is written.  Outputs allocated as zeros when not given, accumulated into when given."""
+        return self._exact(self.L.c8_eval_exact_errors, state, fine, z_u, z_p, phi, E_R, E_C)
+
+    def linearization_errors(self, state, fine, z_u, z_p, phi, E_R=None, E_C=None):
+        """eval_linearization_errors, per element: (E_lin_R, E_lin_C) = what exact_errors adds minus what error_contributions
+        adds at `state`.  Arguments as exact_errors."""
+        return self._exact(self.L.c8_eval_linearization_errors, state, fine, z_u, z_p, phi, E_R, E_C)
 
     # ---- virtual fields method (one-residual systems; calibr8_amd.vfm.VFMProblem drives these) ----------------------
     def vfm_set_virtual_field(self, w):

@@ -170,6 +170,8 @@ SYMBOLS = [
     ("c8_eval_qoi", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p]),
     ("c8_eval_cauchy", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p]),
     ("c8_eval_error_contributions", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("c8_eval_exact_errors", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("c8_eval_linearization_errors", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_vfm_set_virtual_field", C.c_int, [C.c_void_p, C.c_void_p]),
     ("c8_vfm_internal_power", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p]),
     ("c8_vfm_forward_sens", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
