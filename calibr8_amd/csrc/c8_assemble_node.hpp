@@ -19,7 +19,9 @@
 //            values -- their gradients in the reference element first, then the point's cached inverse Jacobian (nine
 //            coalesced loads) --, closed form (radial return, consistent tangent), the row node's record of the point into
 //            LDS, the point's share of the node's residual; the lane of the element's local node 0 stores the converged
-//            local state
+//            local state.  The loads of a phase are issued one dependent round trip ahead of it where they depend on the
+//            element alone (NodeLane): the point's inverse Jacobian, previous state and weights beside the connectivity, the
+//            first rows phase B reads under the closed form
 //   phase B  lane = (element s of the node, column node m)   the 4 x 4 block d R_(node,.) / d x_(m,.) summed over the
 //            element's eight points: 16 accumulators
 //   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order.  The
@@ -85,12 +87,21 @@ C8_HD double const* at_byte(double const* p, int off) { return reinterpret_cast<
 #define C8_TUNE_NODE_HAHEAD 3
 #endif
 
+// Loads issued one phase ahead of their use and carried in the lane record: lane (s, m) of phase A1 is lane (s, point m) of
+// phase A2 and lane (s, column node m) of phase B, so a lane issues its own later loads as soon as it knows its element.
+// NODE_HQ_EARLY: rows of the skewed dN/dx table fetched under the closed form for phase B (the third row of the look-ahead
+// takes the forward kernel from 124 to 129 registers, three wavefronts per SIMD instead of four: slower)
+constexpr int NODE_NXI = 7;  // entries of the local state a lane carries (small_J2)
+constexpr int NODE_HQ_EARLY = 2;
+static_assert(NODE_HQ_EARLY <= C8_TUNE_NODE_HAHEAD, "the rows fetched early are rows of phase B's look-ahead");
 template <int MAXDEG> struct NodeLane {
   static constexpr int N00 = (9 * MAXDEG + 63) / 64, N01 = (3 * MAXDEG + 63) / 64;
   double J[16];
   double a00[N00], a01[N01], a10[N01], a11;  // current values of this lane's CSR entries
   double bold;                               // ... and of its residual entry (lanes 0..3)
   double rs;
+  double G[9], xo[NODE_NXI], w, h;           // A1 -> A2: the point's inverse Jacobian, previous state (forward), weight; the element's size
+  double hq[NODE_HQ_EARLY][3];               // A2 -> B: the column node's dN/dx at the first steps of phase B
   int e, a, pos;
   bool valid;
 };
@@ -154,6 +165,7 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
   using SH = NodeShared<E, Model, MAXDEG, MANY>;
   using NL_ = NodeLane<MAXDEG>;
   constexpr int NL = Model::NLOC, NR = SH::NR;
+  static_assert(NL <= NODE_NXI, "NodeLane::xo holds a point's local state");
   static_assert(E::NN == 8 && E::NP0 == 8 && E::SAME_POINTS, "row-per-node kernel: hex8-like element");
   static_assert(!Mechanics::USES_U && !Model::FINITE_DEF, "row-per-node kernel: small-strain weak form without u terms");
   C8_NSTAMP(6);
@@ -199,9 +211,24 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       int const e = packed >> 3, a = packed & 7;
       r.e = e;
       r.a = a;
+      int const nd = mt.conn[(size_t)e * E::NN + m];  // first: it gates the loads of u and p
       // phase B's operand of this lane (column node m): position of m in the node's graph row
       r.pos = ga.pos[((size_t)e * E::NN + m) * E::NN + a];
-      int const nd = mt.conn[(size_t)e * E::NN + m];
+      // what this lane needs in phase A2 as point m of its element, issued one round trip early: the wait for nd leaves
+      // these outstanding (the counter of outstanding loads is in order), they return under the fetch of u and p.
+      // Adjoint: the previous state and the history entries stay in A2 (issued here they changed K3's rounding)
+      {
+        double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
+        C8_UNROLL
+        for (int c = 0; c < 9; ++c) r.G[c] = t[SHAPE_JINV + 8 * c + m];
+        if constexpr (!ADJ) {
+          size_t const q0 = ((size_t)e * E::NP0 + m) * NL;
+          C8_UNROLL
+          for (int j = 0; j < NL; ++j) r.xo[j] = fa.xi_prev[q0 + j];
+        }
+        r.w = t[SHAPE_WDV + m];
+        r.h = t[SHAPE_H];
+      }
       double* const nv = sh.nodal[s][m];
       nv[0] = fa.u[(size_t)nd * 3 + 0]; nv[1] = fa.u[(size_t)nd * 3 + 1]; nv[2] = fa.u[(size_t)nd * 3 + 2];
       nv[3] = fa.p[nd];
@@ -218,13 +245,13 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
       size_t const q0 = ((size_t)e * E::NP0 + pt) * NL;
       // the point's inverse Jacobian G[3 k + d] = d xi_k / d x_d (the eight lanes of an element read 64 contiguous bytes per
-      // component) and, forward, its previous state: issued ahead of the interpolation, which reads LDS only
+      // component) and, forward, its previous state: fetched by this lane in phase A1
       double G[9], xi_old[NL];
       C8_UNROLL
-      for (int c = 0; c < 9; ++c) G[c] = t[SHAPE_JINV + 8 * c + pt];
+      for (int c = 0; c < 9; ++c) G[c] = r.G[c];
       if constexpr (!ADJ) {
         C8_UNROLL
-        for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
+        for (int j = 0; j < NL; ++j) xi_old[j] = r.xo[j];
       }
       // adjoint assembly: this point's history entries (f at the node's four rows, g), fetched under the interpolation
       double fh4[4] = {0., 0., 0., 0.}, gx[NL];
@@ -284,14 +311,17 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
         for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
       }
       int const es = mt.elem_set ? mt.elem_set[e] : 0;
+      // phase B's first rows of the skewed dN/dx table for this lane as column node pt, fetched under the closed form
+      C8_UNROLL
+      for (int k = 0; k < NODE_HQ_EARLY; ++k) { r.hq[k][0] = t[k * 24 + pt * 2 + 0]; r.hq[k][1] = t[k * 24 + pt * 2 + 1]; r.hq[k][2] = t[k * 24 + 16 + pt]; }
       typename Model::ClosedForm cf;
-      Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, t[SHAPE_H], ms.stab_mult, cf, true);
+      Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, r.h, ms.stab_mult, cf, true);
       if (!ADJ && a == 0) {  // local->scatter (local_residual.cpp:624-631): once per element, by the wavefront of its first node
         C8_UNROLL
         for (int j = 0; j < NL; ++j) fa.xi[q0 + j] = cf.xi[j];
       }
       C8_NSTAMP(8);
-      double const w = t[SHAPE_WDV + pt];
+      double const w = r.w;
       double Na;
       if constexpr (ADJ) Na = HexShape<E>::of_point(pt).at_node(a);
       else Na = sh.nshape[hex_code(a) ^ pt ^ 7];
@@ -342,13 +372,16 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       HexShape<E> Nn;  // adjoint only
       if constexpr (ADJ) Nn = HexShape<E>::of_node(m);
       // dN_m/dx of this lane's column node: at step i the element's eight lanes read row i of the skewed table, this lane
-      // the entry of point (i - m) mod 8; C8_TUNE_NODE_HAHEAD steps ahead of the arithmetic (the element's table is in L1 /
-      // L2 by now).  off = 8 pt rotates from step to step; multiplied, it addresses the point's record and the node's shape
-      // value at the point
+      // the entry of point (i - m) mod 8; C8_TUNE_NODE_HAHEAD steps ahead of the arithmetic, the first NODE_HQ_EARLY rows
+      // fetched in phase A2.  off = 8 pt rotates from step to step; multiplied, it addresses the point's record and the
+      // node's shape value at the point
       constexpr int AH = C8_TUNE_NODE_HAHEAD;
       double hq[AH + 1][3];
       C8_UNROLL
-      for (int k = 0; k < AH; ++k) { hq[k][0] = t[k * 24 + m * 2 + 0]; hq[k][1] = t[k * 24 + m * 2 + 1]; hq[k][2] = t[k * 24 + 16 + m]; }
+      for (int k = 0; k < AH; ++k) {
+        if (k < NODE_HQ_EARLY) { hq[k][0] = r.hq[k][0]; hq[k][1] = r.hq[k][1]; hq[k][2] = r.hq[k][2]; }
+        else { hq[k][0] = t[k * 24 + m * 2 + 0]; hq[k][1] = t[k * 24 + m * 2 + 1]; hq[k][2] = t[k * 24 + 16 + m]; }
+      }
       int off = ((0 - m) & 7) * 8;
       int const cm8 = (hex_code(m) ^ 7) * 8;  // forward: off ^ cm8 is the byte offset of N_m at point off / 8 in nshape
       C8_UNROLL

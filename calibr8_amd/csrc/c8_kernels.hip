@@ -465,7 +465,10 @@ template <class E> static hipError_t launch_gather_rows(GatherArgs const& ga, in
 // before its index and shape-value bookkeeping was stripped; with stripes of 256 the kernels without that
 // bookkeeping took 4.22 / 5.11-5.14 ms beside 4.40 / 5.15-5.17 ms of their predecessors in one call (profiles/README.md,
 // node_image_*).  The present kernels take phase A's gradients from the cached inverse Jacobian instead of the dN/dx table:
-// 3.68 / 4.51 ms beside 4.18 / 5.21 ms of those in one call (last part; profiles/README.md, jinv_*).
+// 3.68 / 4.51 ms beside 4.18 / 5.21 ms of those in one call (profiles/README.md, jinv_*).  They also issue phase
+// A2's table and state loads beside the connectivity and two of phase B's first rows under the closed form (same loads, same
+// bits, one dependent round trip earlier each): 3.54 / 4.35 ms beside 3.61 / 4.44 ms in one call (last part;
+// profiles/README.md, chain_*).
 #ifndef C8_NODE_WAVES
 #define C8_NODE_WAVES 3
 #endif
