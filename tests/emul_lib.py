@@ -41,6 +41,7 @@ class Emul:
         self.local_type, self.stab_mult = local_type, stab_mult
         self.max_iters, self.abs_tol, self.rel_tol = max_iters, abs_tol, rel_tol
         self.nnodes, self.nelems, self.nn, self.npts, self.nloc = o.nnodes, o.nelems, o.nn, o.npts, o.nloc
+        self.ndims, self.nres = o.ndims, o.nres  # read by the host drivers (fe_driver.neq_of, nres_of)
         self.rowptr, self.colidx = o.rowptr, o.colidx
         self.params = o.params
         self.active = np.zeros((o.nsets, 10), dtype=np.int32)
