@@ -32,6 +32,34 @@ def brick_partition(nx, ny, nz, px, py, pz):
     return part
 
 
+def spr_build_host(elem_type, coords, conn):
+    """The set-up of Assembler.spr_recover on the host (c8_spr_build_host; needs no GPU): dict of patch_ptr, patch_elems, g,
+    h, stages as in Assembler.spr_patches.  A patch that cannot be completed raises C8Error; its `node` is the node."""
+    L = _l.load_library()
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    conn = np.ascontiguousarray(conn, dtype=np.int32)
+    nnodes, nelems, T = len(coords), len(conn), (3 if int(elem_type) == _l.C8_ELEM_TRI3 else 4)
+    assert coords.shape == (nnodes, 3) and conn.shape == (nelems, int(elem_type))
+    ptr = np.zeros(nnodes + 1, dtype=np.int64)
+    bad = C.c_int32(-1)
+
+    def call(elems, cap, g, h, st):
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        rc = L.c8_spr_build_host(int(elem_type), nnodes, nelems, coords.ctypes.data_as(_l.dp), conn.ctypes.data_as(_l.i32p),
+                                 ptr.ctypes.data_as(_l.i64p), p(elems, _l.i32p), cap, p(g, _l.dp), p(h, _l.dp), p(st, _l.i32p),
+                                 C.byref(bad))
+        if rc < 0:
+            err = _l.C8Error(rc, L.c8_last_error().decode())
+            err.node = bad.value
+            raise err
+
+    call(None, 0, None, None, None)
+    elems = np.zeros(int(ptr[-1]), dtype=np.int32)
+    g, h, st = np.zeros((nnodes, T)), np.zeros(nnodes), np.zeros(nnodes, dtype=np.int32)
+    call(elems, len(elems), g, h, st)
+    return {"patch_ptr": ptr, "patch_elems": elems, "g": g, "h": h, "stages": st}
+
+
 class LinearSystem:
     """A[i][j] CSR values and b[i] in GHOST distribution, as device tensors (la->A, la->b)."""
 
@@ -330,6 +358,58 @@ class Assembler:
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and out.numel() == self.nelems * self.npts * 9
         st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
         self._rc(self.L.c8_eval_cauchy(self.h, C.byref(st), C.c_void_p(out.data_ptr())))
+        return out
+
+    def _point_field(self, t, what):
+        torch = self.torch
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64, what
+        return t
+
+    def spr_recover(self, ip_field, out=None):
+        """spr_recovery (cspr.cpp): a point field [nelems, npts, ...] brought to the nodes [nnodes, ...] by superconvergent
+        patch recovery (the trailing dimensions, at most 16 entries together, are the components).  `out`, if given, is
+        overwritten and returned."""
+        torch = self.torch
+        self._point_field(ip_field, "ip_field")
+        assert ip_field.dim() >= 2 and tuple(ip_field.shape[:2]) == (self.nelems, self.npts), tuple(ip_field.shape)
+        comp = tuple(ip_field.shape[2:])
+        ncomp = int(np.prod(comp)) if comp else 1
+        if out is None:
+            out = torch.empty((self.nnodes,) + comp, dtype=torch.float64, device=self.device)
+        self._point_field(out, "out")
+        assert out.numel() == self.nnodes * ncomp
+        self._rc(self.L.c8_spr_recover(self.h, ncomp, C.c_void_p(ip_field.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def interpolate_to_points(self, nodal, out=None):
+        """interpolate_to_cell_center at the local-state points: a nodal field [nnodes, ...] evaluated by the element's
+        shape values, [nelems, npts, ...].  `out`, if given, is overwritten and returned."""
+        torch = self.torch
+        self._point_field(nodal, "nodal")
+        assert nodal.dim() >= 1 and nodal.shape[0] == self.nnodes, tuple(nodal.shape)
+        comp = tuple(nodal.shape[1:])
+        ncomp = int(np.prod(comp)) if comp else 1
+        if out is None:
+            out = torch.empty((self.nelems, self.npts) + comp, dtype=torch.float64, device=self.device)
+        self._point_field(out, "out")
+        assert out.numel() == self.nelems * self.npts * ncomp
+        self._rc(self.L.c8_interpolate_to_points(self.h, ncomp, C.c_void_p(nodal.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def spr_patches(self):
+        """The recovery tables of this mesh as host arrays (copies): dict of patch_ptr [nnodes + 1], patch_elems, g
+        [nnodes, ndims + 1], h [nnodes], stages [nnodes] and setup (ms device, ms host, ms upload, flagged nodes)."""
+        kinds = (("patch_ptr", np.int64), ("patch_elems", np.int32), ("g", np.float64), ("h", np.float64),
+                 ("stages", np.int32), ("setup", np.float64))
+        out = {}
+        for which, (name, dt) in enumerate(kinds):
+            n, data = C.c_int64(), C.c_void_p()
+            _l.check(self.L.c8_spr_table(self.h, which, C.byref(n), C.byref(data)))
+            a = np.empty(n.value, dtype=dt)
+            if n.value:
+                C.memmove(a.ctypes.data, data, a.nbytes)
+            out[name] = a
+        out["g"] = out["g"].reshape(self.nnodes, self.ndims + 1)
         return out
 
     def error_contributions(self, u, p, u_prev, p_prev, xi_prev, xi, z_u, z_p, phi, E_R=None, E_C=None):

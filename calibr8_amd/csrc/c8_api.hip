@@ -202,6 +202,7 @@ void c8_destroy(c8_ctx* c) {
   void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
   for (void* b : bufs) (void)hipFree(b);
   c8_krylov_release(c);
+  c8_spr_release(c);
   delete c;
 }
 
@@ -674,6 +675,19 @@ int c8_eval_qoi(c8_ctx* c, const c8_state* st, double* J) {
   int rc = c8_qoi_prepare(c, fa);
   if (rc || (rc = c8_qoi_surface(c, st->x[0], J, nullptr)) || (rc = c8_qoi_postprocess(c, J))) return rc;
   return c->async ? C8_OK : c8_status(c);
+}
+
+int c8_spr_build_host(int elem_type, int32_t num_nodes, int32_t num_elems, const double* coords, const int32_t* conn, int64_t* patch_ptr,
+                      int32_t* patch_elems, int64_t capacity, double* g, double* h, int32_t* stages, int32_t* failed_node) {
+  int32_t bad = -1;
+  if (failed_node) *failed_node = -1;
+  if (elem_type != C8_ELEM_TET4 && elem_type != C8_ELEM_HEX8 && elem_type != C8_ELEM_TRI3)
+    return fail(C8_ERR_UNSUPPORTED, "c8_spr_build_host: elem_type must be C8_ELEM_TRI3, C8_ELEM_TET4 or C8_ELEM_HEX8");
+  if (num_nodes <= 0 || num_elems <= 0 || !coords || !conn || !patch_ptr) return fail(C8_ERR_ARG, "c8_spr_build_host: bad argument");
+  std::string const err = spr_build_host(elem_type, num_nodes, num_elems, coords, conn, patch_ptr, patch_elems, capacity, g, h, stages, &bad);
+  if (failed_node) *failed_node = bad;
+  if (!err.empty()) return fail(C8_ERR_ARG, "c8_spr_build_host: " + err);
+  return C8_OK;
 }
 
 int c8_brick_mesh(int nx, int ny, int nz, double lx, double ly, double lz, double* coords, int32_t* conn) {

@@ -34,6 +34,20 @@ struct c8_kry_level {
   double* d_vec = nullptr;            // right-hand side and iterate of the level, [n][NC] each
 };
 
+// superconvergent patch recovery (c8_spr.hip): the tables of c8_spr_recover, built at its first call
+struct c8_spr_tables {
+  bool built = false;
+  double* d_pts = nullptr;            // [nelems][coupled points][ndims] sample positions
+  double* d_g = nullptr;              // [nnodes][ndims + 1]
+  double* d_h = nullptr;              // [nnodes]
+  int64_t* d_patch_ptr = nullptr;     // [nnodes + 1]
+  int32_t* d_patch_elems = nullptr;
+  std::vector<int64_t> patch_ptr;     // host copies (c8_spr_table)
+  std::vector<int32_t> patch_elems, stages;
+  std::vector<double> g, h;
+  double info[4] = {0., 0., 0., 0.};  // set-up: ms on the device, ms on the host, ms of upload, flagged nodes
+};
+
 struct c8_ctx {
   // (namespace c8 types)
   c8::HostMesh mesh;
@@ -178,7 +192,9 @@ struct c8_ctx {
   std::vector<double> kry_pc_x;      // [kry_pc_nagg][3] centroids of this rank's aggregates
   int kry_pl_for = -1;               // num_owned the levels were built for (-1: not built; reset by c8_halo_attach and c8_krylov_set_multilevel)
   std::vector<c8_kry_level> kry_pl_levels;            // [k] is level k + 1; freed by c8_krylov_release
+  c8_spr_tables spr;
 };
+void c8_spr_release(c8_ctx* c);      // c8_spr.hip: frees the recovery tables
 void c8_krylov_release(c8_ctx* c);   // c8_krylov.hip: what c8_destroy cannot free with hipFree
 // c8_embedded.hip: grad[c8_num_active_params ..] += the weight gradient (hybrid model; no-op for the others)
 int c8_embedded_param_gradient(c8_ctx* c, const c8_state* st, const double* phi, double* grad);

@@ -4,6 +4,12 @@
 #include <algorithm>
 #include <cstring>
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // the library compiles this file as HIP: the C8_HD qualifiers of c8_spr.hpp's headers
+#endif
+
+#include "c8_spr.hpp"
+
 namespace c8 {
 
 std::string build_node_graph(HostMesh const& m, HostGraph& g) {
@@ -184,6 +190,28 @@ void brick_partition(int nx, int ny, int nz, int px, int py, int pz, std::vector
         int const a = (int)((int64_t)i * px / nx), b = (int)((int64_t)j * py / ny), c = (int)((int64_t)k * pz / nz);
         elem_part[e] = (c * py + b) * px + a;
       }
+}
+
+// the whole set-up of c8_spr_recover on the host (c8_spr.hpp): no context, no device
+std::string spr_build_host(int elem_type, int nnodes, int nelems, double const* coords, int32_t const* conn, int64_t* patch_ptr,
+                           int32_t* patch_elems, int64_t capacity, double* g, double* h, int32_t* stages, int32_t* failed_node) {
+  *failed_node = -1;
+  int const nn = elem_type;  // 3, 4, 8: the type ids are the node counts
+  for (size_t q = 0; q < (size_t)nelems * nn; ++q)
+    if (conn[q] < 0 || conn[q] >= nnodes) return "connectivity entry out of range";
+  std::vector<int32_t> ne_ptr, ne;
+  spr_node_elems(nnodes, nelems, nn, conn, ne_ptr, ne);
+  std::vector<double> pts((size_t)nelems * spr_np0(elem_type) * spr_dim(elem_type));
+  spr_points_host(elem_type, nelems, conn, coords, pts.data());
+  SprMesh const m{elem_type, nnodes, nelems, coords, conn, ne_ptr.data(), ne.data(), 0, pts.data()};
+  int const bad = spr_build_all(m, patch_ptr, patch_elems, capacity, g, h, stages, nullptr);
+  if (bad == -2) return "capacity is smaller than the patch table (call with patch_elems = NULL for patch_ptr)";
+  if (bad >= 0) {
+    *failed_node = bad;
+    return "the patch of node " + std::to_string(bad) +
+           " cannot be completed: it stopped growing without enough points of full rank (all hope is lost)";
+  }
+  return "";
 }
 
 }  // namespace c8

@@ -67,4 +67,9 @@ void make_brick(int nx, int ny, int nz, double lx, double ly, double lz, HostMes
 // reference's offline ParMETIS/Zoltan split, which is not available here).
 void brick_partition(int nx, int ny, int nz, int px, int py, int pz, std::vector<int32_t>& elem_part);
 
+// Superconvergent patch recovery, the whole set-up on the host (c8_spr.hpp; arguments of c8_spr_build_host in c8.h).
+// Returns an empty string, or an error message; *failed_node is the node whose patch cannot be completed, else -1.
+std::string spr_build_host(int elem_type, int nnodes, int nelems, double const* coords, int32_t const* conn, int64_t* patch_ptr,
+                           int32_t* patch_elems, int64_t capacity, double* g, double* h, int32_t* stages, int32_t* failed_node);
+
 }  // namespace c8

@@ -193,3 +193,10 @@ def model_form_error_verify(primal, fine_primal, solver=None):
     return ModelFormErrorVerify(J_H=J_H, J_h=J_h, eta=eta, E_lin_R=E_lin_R, E_lin_C=E_lin_C, E_exact=J_h - J_H,
                                 E_computed=eta + E_lin_R + E_lin_C, allowance=allowance, traction=t, z_norm=z_norm,
                                 phi_norm=phi_norm, fields=F)
+
+
+def spr_smooth(asm, nodal, out=None):
+    """The body of the reference's perform_SPR loop (main_spr_error.cpp) for one nodal field [nnodes, ...]: interpolate it to
+    the local-state points (interpolate_to_cell_center), recover it to the nodes by superconvergent patch recovery
+    (spr_recovery).  Affine fields come back unchanged; `out`, if given, is overwritten and returned."""
+    return asm.spr_recover(asm.interpolate_to_points(nodal), out=out)

@@ -172,6 +172,10 @@ SYMBOLS = [
     ("c8_eval_error_contributions", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_eval_exact_errors", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("c8_eval_linearization_errors", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(State), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("c8_spr_recover", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("c8_interpolate_to_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("c8_spr_table", C.c_int, [C.c_void_p, C.c_int, i64p, C.POINTER(C.c_void_p)]),
+    ("c8_spr_build_host", C.c_int, [C.c_int, C.c_int32, C.c_int32, dp, i32p, i64p, i32p, C.c_int64, dp, dp, i32p, i32p]),
     ("c8_vfm_set_virtual_field", C.c_int, [C.c_void_p, C.c_void_p]),
     ("c8_vfm_internal_power", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p]),
     ("c8_vfm_forward_sens", C.c_int, [C.c_void_p, C.POINTER(State), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -276,6 +276,22 @@ class PrimalDriver:
             return self.torch.zeros(asm.nelems, asm.npts, 3, 3, dtype=self.torch.float64, device=asm.device)
         return asm.cauchy(self.u[step], self.p[step], self.u[step - 1], self.p[step - 1], self.xi[step - 1], self.xi[step])
 
+    def nodal_cauchy(self, step):
+        """The stress field of a solved step recovered to the nodes (Assembler.spr_recover of cauchy(step)): [nnodes, 3, 3]
+        on the device; zeros for step 0, like cauchy."""
+        asm = self.asm
+        if not 0 <= step < len(self.u):
+            raise IndexError("step %d has not been solved" % step)
+        if step == 0:
+            return self.torch.zeros(asm.nnodes, 3, 3, dtype=self.torch.float64, device=asm.device)
+        return asm.spr_recover(self.cauchy(step))
+
+    def nodal_local(self, step):
+        """The local state xi[step] recovered to the nodes: [nnodes, nloc] on the device."""
+        if not 0 <= step < len(self.xi):
+            raise IndexError("step %d has not been solved" % step)
+        return self.asm.spr_recover(self.xi[step])
+
     def set_measured(self, u_meas, loads):
         """Calibration objective: measured displacements (device tensors) and loads per step, index 0 unused."""
         self.measured = (u_meas, loads)

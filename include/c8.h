@@ -787,6 +787,45 @@ int c8_transform_params(int n, const double* values, const int32_t* kind, const 
 int c8_transform_gradient(int n, const double* grad, const double* values, const int32_t* kind, const double* a,
                           const double* b, double* out);
 
+/* ---- superconvergent patch recovery (cspr.cpp: spr_recovery) ------------------------------
+ * A point field [num_elems][c8_num_local_points][ncomp] brought to the nodes [num_nodes][ncomp]: per node and component
+ * the least-squares polynomial 1, x, y(, z) through the samples of the node's patch, evaluated at the node.  Samples are
+ * the local-state points (ip set 0) at their isoparametric positions.  The patch of a node starts as its elements
+ * (getInitialPatch) and is accepted when points_per_element * |patch| >= 1.1 * terms and the fit matrix, in coordinates
+ * centred at the node and scaled by h = max_s |x_s - x_n|_inf, has no |R_kk| <= 1e-8 sqrt(samples) in its QR
+ * factorisation; otherwise it grows as expandAsNecessary does, with "shares an entity of dimension d-1, ..., 0 with an
+ * element of the frozen patch" read as "has at least m nodes in common": m = 3, 2, 1 (tet4), 4, 2, 1 (hex8), 2, 1 (tri3),
+ * tested after every stage, repeated from the grown patch while it grows.  A patch that stops growing unaccepted fails
+ * the call: C8_ERR_ARG, the message names the node ("all hope is lost").  The linear fit only (the mesh is linear).
+ *
+ * c8_spr_recover: ip_field and nodal are DEVICE pointers, the layouts of sigma (ncomp 9) and xi (ncomp =
+ * c8_num_local_dofs); nodal is OVERWRITTEN, ip_field is not written.  1 <= ncomp <= 16 and non-null pointers, else
+ * C8_ERR_ARG.  The tables (patches, one coefficient vector g [num_dims + 1] and one h per node) depend on the mesh alone:
+ * they are built at the first call (device fit of every node, host expansion of the few nodes it flags) and kept.  A
+ * call is one kernel without atomics: two calls give the same bytes.  Stream, async mode and return value as
+ * c8_eval_cauchy (the first call also waits for its set-up).  With a halo attached (c8_halo_attach): C8_ERR_UNSUPPORTED,
+ * patches cross part boundaries. */
+int c8_spr_recover(c8_ctx* ctx, int ncomp, const double* ip_field, double* nodal);
+/* interpolate_to_cell_center (main_spr_error.cpp), at the local-state points: ip_field [num_elems][c8_num_local_points]
+ * [ncomp] = sum_a N_a(point) nodal[node a][ncomp] (tet4, tri3: the centroid, as there).  DEVICE pointers, ip_field
+ * OVERWRITTEN; arguments, stream, async mode and return value as c8_spr_recover.  Not collective: needs the ghost entries
+ * of nodal imported, like every other entry point. */
+int c8_interpolate_to_points(c8_ctx* ctx, int ncomp, const double* nodal, double* ip_field);
+/* Diagnostic / test access to the HOST copies of the tables, in the manner of c8_halo_table (built if needed; valid
+ * until c8_destroy): which = 0 patch_ptr (int64 [num_nodes + 1]), 1 patch_elems (int32, ascending per node), 2 g (double
+ * [num_nodes][num_dims + 1]), 3 h (double [num_nodes]), 4 expansion stages run per node (int32 [num_nodes]; 0: the
+ * node's own elements were enough), 5 set-up record (double [4]: ms device fit and read-back, ms host expansion and table,
+ * ms upload, nodes the device fit flagged).  C8_ERR_UNSUPPORTED with a halo attached. */
+int c8_spr_table(c8_ctx* ctx, int which, int64_t* n, const void** data);
+/* The same set-up on the host with the same functions (c8_spr.hpp): no context, no device, HOST arrays.  patch_ptr
+ * [num_nodes + 1] is always filled; with patch_elems == NULL nothing else is needed (the caller sizes patch_elems from
+ * patch_ptr[num_nodes]); otherwise patch_elems has `capacity` entries (too few: C8_ERR_ARG) and g [num_nodes][dims + 1],
+ * h [num_nodes], stages [num_nodes] are filled where not NULL.  A patch that cannot be completed: C8_ERR_ARG,
+ * *failed_node (may be NULL; else -1) is the node, the message names it. */
+int c8_spr_build_host(int elem_type, int32_t num_nodes, int32_t num_elems, const double* coords, const int32_t* conn,
+                      int64_t* patch_ptr, int32_t* patch_elems, int64_t capacity, double* g, double* h, int32_t* stages,
+                      int32_t* failed_node);
+
 /* ---- host helpers for synthetic problems -------------------------------- */
 /* Structured hex8 brick; coords [(nx+1)(ny+1)(nz+1)][3], conn [nx*ny*nz][8] (host arrays). */
 int c8_brick_mesh(int nx, int ny, int nz, double lx, double ly, double lz, double* coords, int32_t* conn);
