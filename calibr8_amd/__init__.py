@@ -6,7 +6,7 @@ by the tests and the bench: ctypes bindings plus an `Assembler` whose arrays are
 in HBM.  There is no CPU execution path: creating an `Assembler` without a HIP device raises.
 """
 from .lib import C8Error, load_library  # noqa: F401
-from .assembly import Assembler, LinearSystem, brick_mesh, brick_partition, spr_build_host  # noqa: F401
+from .assembly import Assembler, LinearSystem, brick_mesh, brick_partition, local_dof, spr_build_host  # noqa: F401
 from .primal import PrimalDriver, adjoint_gradient, device_solver, distributed_device_solver, scipy_solver  # noqa: F401
 from .inverse import FEMUProblem, InverseProblem, lbfgs_minimize  # noqa: F401
 from .vfm import VFMProblem  # noqa: F401

@@ -60,6 +60,20 @@ def spr_build_host(elem_type, coords, conn):
     return {"patch_ptr": ptr, "patch_elems": elems, "g": g, "h": h, "stages": st}
 
 
+# the flat position of the hardening variable alpha in a point's local state where it is not the last unknown
+_ALPHA_DOF = {"hypo_hill_plane_strain": 3, "hypo_hill_plane_stress": 3}
+_NO_ALPHA = ("elastic", "isotropic_elastic")
+
+
+def local_dof(local_type, nloc, name):
+    """The flat index into a point's local state xi of the scalar local unknown `name` of the model `local_type` with
+    `nloc` local unknowns (the reference names a scalar local residual; the library indexes xi): "alpha", the hardening
+    variable, of the plasticity models."""
+    if name != "alpha" or local_type in _NO_ALPHA:
+        raise ValueError("local_dof: %s has no scalar local unknown %r" % (local_type, name))
+    return _ALPHA_DOF.get(local_type, nloc - 1)
+
+
 class LinearSystem:
     """A[i][j] CSR values and b[i] in GHOST distribution, as device tensors (la->A, la->b)."""
 
@@ -528,6 +542,25 @@ class Assembler:
         _l.check(self.L.c8_set_qoi_calibration(self.h, C.byref(d)))
         self.objective = ("calibration", f.tobytes(), f.shape, tuple(float(w) for w in weights), float(balance), int(coord_idx),
                           float(coord_value), float(coord_tol), int(comp), float(dt_over_T))
+
+    def set_qoi_subdomain(self, kind, elem_set, index=0):
+        """Subdomain objective over the elements of one element set (c8_set_qoi_subdomain): kind = "avg_stress" (the norm
+        of the deviatoric Cauchy stress), "avg_local_var" (local dof `index`, a flat position in a point's local state or a
+        name that local_dof() knows) or "disp_comp" (displacement component `index`), or the C8_QOI_* value.  Plain
+        integrals, not divided by the volume."""
+        kind = _l.C8_QOI_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if isinstance(index, str):
+            index = local_dof(self.local_type, self.nloc, index)
+        d = _l.SubdomainQoiDesc(kind, int(elem_set), int(index))
+        _l.check(self.L.c8_set_qoi_subdomain(self.h, C.byref(d)))
+        self.objective = ("subdomain", kind, int(elem_set), int(index) if kind != _l.C8_QOI_AVG_STRESS else 0)
+
+    def set_qoi_reaction(self, coord_idx=1, coord_value=0.0, coord_tol=1e-8, comp=1):
+        """Reaction objective (reaction.cpp without torque): the internal force component `comp` summed over the nodes with
+        |x[coord_idx] - coord_value| < coord_tol.  On a multi-part mesh call set_allreduce first."""
+        d = _l.ReactionDesc(int(coord_idx), float(coord_value), float(coord_tol), int(comp))
+        _l.check(self.L.c8_set_qoi_reaction(self.h, C.byref(d)))
+        self.objective = ("reaction", int(coord_idx), float(coord_value), float(coord_tol), int(comp))
 
     def set_allreduce(self, dist, num_parts):
         """Multi-part objective sums: `dist` = an initialised torch.distributed module (SUM all-reduce of host doubles)."""

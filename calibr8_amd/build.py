@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libc8.so")
 KERNEL_PARTS = 6  # c8_kernels.hip is compiled once per group of template instantiations (-DC8_KERNEL_PART=n), in parallel
 SOURCES = ["c8_kernels.hip:%d" % k for k in range(KERNEL_PARTS)] + ["c8_api.hip", "c8_primal.hip", "c8_qoi.hip", "c8_halo.hip",
                                                                       "c8_vfm.hip", "c8_embedded.hip", "c8_krylov.hip", "c8_cauchy.hip", "c8_error.hip",
-                                                                      "c8_exact.hip", "c8_spr.hip",
+                                                                      "c8_exact.hip", "c8_spr.hip", "c8_qoi_point.hip",
                                                                       "c8_host.cpp", "c8_lbfgs.cpp"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics"]
 

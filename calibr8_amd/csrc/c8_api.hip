@@ -199,7 +199,7 @@ void c8_destroy(c8_ctx* c) {
   for (hipEvent_t e : c->ev_asm) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_sum) (void)hipEventDestroy(e);
   if (c->sum_stream) (void)hipStreamDestroy(c->sum_stream);
-  void* bufs[] = {c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
+  void* bufs[] = {c->d_qoi_rec, c->d_qoi_part, c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
   for (void* b : bufs) (void)hipFree(b);
   c8_krylov_release(c);
   c8_spr_release(c);
@@ -615,8 +615,13 @@ int c8_assemble_adjoint_jacobian(c8_ctx* c, const c8_state* st, double* g, const
   // two parts, the second part would overwrite it
   if (c->assign_mode && c->qoi_kind == 1 && c->early_end > c->early_begin && c->scatter_mode == C8_SCATTER_GATHER)
     return fail(C8_ERR_UNSUPPORTED, "c8_assemble_adjoint_jacobian: assign mode with two-part row sums and the calibration objective");
+  // ... and so is -dJ/dx of a subdomain objective (c8_qoi_point.hip)
+  if (c->assign_mode && c->qoi_kind == 2 && c->early_end > c->early_begin && c->scatter_mode == C8_SCATTER_GATHER)
+    return fail(C8_ERR_UNSUPPORTED, "c8_assemble_adjoint_jacobian: assign mode with two-part row sums and a subdomain objective");
   int rc = c8_qoi_prepare(c, field_args(st));  // preprocess_qoi (evaluations.cpp:365)
   if (rc) return rc;
+  // subdomain objective: the kernels below run with a zero objective; g -= dJ/dxi before they read g
+  if (c->qoi_kind == 2 && (rc = c8_subqoi_pre(c, field_args(st), g))) return rc;
   AdjointArgs aa{g, const_cast<double*>(f), nullptr, nullptr, nullptr, nullptr, c->d_active, c8_qoi_args(c)};
   LaunchFn fn = c->ks.adjoint_jacobian;
   if (c->ks.adjoint_jacobian_wave && c->kernel_variant != C8_KERNEL_SLOT) fn = c->ks.adjoint_jacobian_wave;
@@ -626,6 +631,7 @@ int c8_assemble_adjoint_jacobian(c8_ctx* c, const c8_state* st, double* g, const
   c->async = async;
   if (rc) return rc;
   if ((rc = c8_qoi_surface(c, st->x[0], nullptr, sys->b[0]))) return rc;
+  if (c->qoi_kind == 2 && (rc = c8_subqoi_post(c, sys->b[0], sys->b[1]))) return rc;
   return async ? C8_OK : c8_status(c);
 }
 
@@ -658,6 +664,7 @@ int c8_param_gradient(c8_ctx* c, const c8_state* st, const double* const z[2], c
   int rc = run(c, fn, field_args(st), aa, SystemArgs{}, false, "c8_param_gradient");
   c->async = async;
   if (rc == C8_OK) rc = c8_embedded_param_gradient(c, st, phi, grad);  // evaluations.cpp:873-879: theta after the active parameters
+  if (rc == C8_OK && c->qoi_kind == 2) rc = c8_subqoi_grad(c, field_args(st), grad);  // dJ/dp of a subdomain objective
   if (rc || async) return rc;
   return c8_status(c);
 }
@@ -671,7 +678,11 @@ int c8_eval_qoi(c8_ctx* c, const c8_state* st, double* J) {
   }
   // calibration (Calibration<double>::evaluate + postprocess): preprocess_qoi (evaluations.cpp:674), the face
   // term, and 1/2 balance dt/T load_mismatch^2
-  if (!st->xi || !st->xi_prev) return fail(C8_ERR_ARG, "c8_eval_qoi: the calibration objective needs the local state");
+  if (!st->xi || !st->xi_prev) return fail(C8_ERR_ARG, "c8_eval_qoi: this objective needs the local state");
+  if (c->qoi_kind == 2 || c->qoi_kind == 3) {
+    int const rcs = c->qoi_kind == 2 ? c8_subqoi_value(c, fa, J) : c8_qoi_reaction_value(c, fa, J);
+    return (rcs || c->async) ? rcs : c8_status(c);
+  }
   int rc = c8_qoi_prepare(c, fa);
   if (rc || (rc = c8_qoi_surface(c, st->x[0], J, nullptr)) || (rc = c8_qoi_postprocess(c, J))) return rc;
   return c->async ? C8_OK : c8_status(c);

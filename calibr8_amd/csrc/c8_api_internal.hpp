@@ -97,8 +97,11 @@ struct c8_ctx {
   int32_t* d_active = nullptr;  // [nsets][10]: {grad offset, n_active, indices...}
   int* d_status = nullptr;
   unsigned long long* d_stamps = nullptr;  // -DC8_STAMPS diagnostic build only
-  // objective: 0 = average displacement, 1 = calibration (c8_qoi.hip)
+  // objective: 0 = average displacement, 1 = calibration, 3 = reaction (c8_qoi.hip), 2 = subdomain (c8_qoi_point.hip)
   int qoi_kind = 0;
+  int sub_kind = 0, sub_set = 0, sub_index = 0;  // c8_subdomain_qoi_desc
+  double* d_qoi_rec = nullptr;      // [nelems][points][QOI_REC] x-records of the points, from the pre-pass to the post-pass
+  double* d_qoi_part = nullptr;     // [8][blocks] per-block partial sums of the value and the gradient kernel
   int32_t* d_cal_faces = nullptr;   // [cal_nfaces][4] node ids of the element faces on the displacement side set
   double* d_cal_S = nullptr;        // [nelems][coupled points][3] load-plane sums of grad N
   double const* d_u_meas = nullptr; // caller's measured displacement of the current step (device)
@@ -205,6 +208,12 @@ c8::QoiArgs c8_qoi_args(c8_ctx const* c);
 int c8_qoi_prepare(c8_ctx* c, c8::FieldArgs const& fa);
 int c8_qoi_surface(c8_ctx* c, double const* u, double* J, double* b0);
 int c8_qoi_postprocess(c8_ctx* c, double* J);
+int c8_qoi_reaction_value(c8_ctx* c, c8::FieldArgs const& fa, double* J);  // *J += the total load / num_parts
+// c8_qoi_point.hip: the subdomain objectives beside the adjoint kernels (qoi_kind == 2)
+int c8_subqoi_value(c8_ctx* c, c8::FieldArgs const& fa, double* J);  // *J += the value of the step
+int c8_subqoi_pre(c8_ctx* c, c8::FieldArgs const& fa, double* g);    // before K3: g -= dJ/dxi
+int c8_subqoi_post(c8_ctx* c, double* b0, double* b1);               // after K3: b -= dJ/dx
+int c8_subqoi_grad(c8_ctx* c, c8::FieldArgs const& fa, double* grad);  // with K5: grad += dJ/dp
 // c8_halo.hip: multi-part helpers for the other translation units
 int c8_parts_allreduce(c8_ctx* c, double* values, int n);  // SUM over the parts: caller's callback, else the halo's communicator; no-op on one part
 int c8_halo_num_owned(c8_halo const* h);

@@ -55,13 +55,19 @@ __global__ void k_add_scalar(double* x, double v) { *x += v; }
 // the point integrand of the adjoint kernels (K3, K5): x, xi or parameter derivatives of the objective
 QoiArgs c8_qoi_args(c8_ctx const* c) {
   if (c->qoi_kind == 0) return QoiArgs{1., 0., 0, nullptr, (double)c->ndims};
+  if (c->qoi_kind == 2) return QoiArgs{0., 0., 0, nullptr, (double)c->ndims};  // subdomain: beside the kernels (c8_qoi_point.hip)
+  if (c->qoi_kind == 3) return QoiArgs{0., 1., c->cal_comp, c->d_cal_S, (double)c->ndims, c->ms.thickness};  // reaction: the load itself
   return QoiArgs{0., c->cal_balance * c->cal_dt_over_T * c->cal_load_mismatch, c->cal_comp, c->d_cal_S, (double)c->ndims, c->ms.thickness};
 }
 
 // preprocess_qoi: the total reaction load of the step and its mismatch with the measured load
+static int total_load(c8_ctx* c, FieldArgs const& fa);
 int c8_qoi_prepare(c8_ctx* c, FieldArgs const& fa) {
-  if (c->qoi_kind == 0) return C8_OK;
+  if (c->qoi_kind != 1) return C8_OK;  // the reaction objective's derivatives do not depend on the load
   if (!c->d_u_meas) return c8_fail(C8_ERR_ARG, "calibration objective: c8_set_measured has not been called");
+  return total_load(c, fa);
+}
+static int total_load(c8_ctx* c, FieldArgs const& fa) {
   QH(hipMemsetAsync(c->d_scalar, 0, sizeof(double), c->stream));
   AdjointArgs aa{nullptr, nullptr, nullptr, nullptr, nullptr, c->d_scalar, c->d_active, QoiArgs{0., 1., c->cal_comp, c->d_cal_S, (double)c->ndims, c->ms.thickness}};
   MeshTables mt{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, nullptr, c->d_params};
@@ -81,7 +87,7 @@ int c8_qoi_prepare(c8_ctx* c, FieldArgs const& fa) {
 
 // the face term: J (nullable) += value, b0 (nullable) -= d value / d u
 int c8_qoi_surface(c8_ctx* c, double const* u, double* J, double* b0) {
-  if (c->qoi_kind == 0 || c->cal_nfaces == 0) return C8_OK;
+  if (c->qoi_kind != 1 || c->cal_nfaces == 0) return C8_OK;
   if (!(c->cal_area > 0.)) return c8_fail(C8_ERR_ARG, "calibration objective: the displacement side set has no area");
   double const scale = (double)c->npts0 * c->cal_dt_over_T / c->cal_area;
   int const n = c->cal_nfaces;
@@ -93,7 +99,7 @@ int c8_qoi_surface(c8_ctx* c, double const* u, double* J, double* b0) {
 
 // Calibration::postprocess on one rank: J += 1/2 balance dt/T load_mismatch^2
 int c8_qoi_postprocess(c8_ctx* c, double* J) {
-  if (c->qoi_kind == 0) return C8_OK;
+  if (c->qoi_kind != 1) return C8_OK;
   // every part adds the load term; the caller's sum over the parts counts it once (J /= PCU_Comm_Peers(), :378)
   double const Jf = 0.5 * c->cal_balance * c->cal_dt_over_T * c->cal_load_mismatch * c->cal_load_mismatch / c->num_parts;
   hipLaunchKernelGGL(k_add_scalar, dim3(1), dim3(1), 0, c->stream, J, Jf);
@@ -101,7 +107,37 @@ int c8_qoi_postprocess(c8_ctx* c, double* J) {
   return C8_OK;
 }
 
+// reaction: the total load of the step, summed over the parts; every part adds 1 / num_parts of it (as the load term above)
+int c8_qoi_reaction_value(c8_ctx* c, FieldArgs const& fa, double* J) {
+  int const rc = total_load(c, fa);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_add_scalar, dim3(1), dim3(1), 0, c->stream, J, c->cal_total_load / c->num_parts);
+  QH(hipGetLastError());
+  return C8_OK;
+}
+
 extern "C" {
+
+int c8_set_qoi_reaction(c8_ctx* c, const c8_reaction_desc* d) {
+  if (!c || !d) return c8_fail(C8_ERR_ARG, "c8_set_qoi_reaction: null argument");
+  if (d->coord_idx < 0 || d->coord_idx >= c->ndims || d->reaction_comp < 0 || d->reaction_comp >= c->ndims)
+    return c8_fail(C8_ERR_ARG, "c8_set_qoi_reaction: coordinate index / component out of range");
+  CalibrationTables t;  // the load plane's sums of grad N; no displacement side set
+  calibration_tables(c->mesh, 0, nullptr, d->coord_idx, d->coord_value, d->coord_tol, t);
+  (void)hipFree(c->d_cal_faces);
+  (void)hipFree(c->d_cal_S);
+  c->d_cal_faces = nullptr;
+  c->d_cal_S = nullptr;
+  QH(hipMalloc((void**)&c->d_cal_S, t.S.size() * sizeof(double)));
+  QH(hipMemcpy(c->d_cal_S, t.S.data(), t.S.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->cal_nfaces = 0;
+  c->cal_area = c->cal_area_local = 0.;
+  c->cal_comp = d->reaction_comp;
+  c->cal_load_meas = c->cal_total_load = c->cal_load_mismatch = 0.;
+  c->d_u_meas = nullptr;
+  c->qoi_kind = 3;
+  return C8_OK;
+}
 
 int c8_set_qoi_avg_disp(c8_ctx* c) {
   if (!c) return c8_fail(C8_ERR_ARG, "c8_set_qoi_avg_disp: null ctx");
@@ -166,7 +202,7 @@ int c8_set_measured(c8_ctx* c, const double* u_meas, double load_meas) {
 int c8_qoi_preprocess(c8_ctx* c, const c8_state* st, double* out) {
   if (!c || !st || !st->x[0] || (c->nres == 2 && !st->x[1]) || !st->xi || !st->xi_prev) return c8_fail(C8_ERR_ARG, "c8_qoi_preprocess: null argument");
   FieldArgs fa{st->x[0], st->x[1], st->x_prev[0], st->x_prev[1], st->xi_prev, st->xi};
-  int const rc = c8_qoi_prepare(c, fa);
+  int const rc = c->qoi_kind == 3 ? total_load(c, fa) : c8_qoi_prepare(c, fa);
   if (rc) return rc;
   if (out) { out[0] = c->cal_area; out[1] = c->cal_total_load; out[2] = c->cal_load_mismatch; }
   return C8_OK;

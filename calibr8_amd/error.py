@@ -158,14 +158,15 @@ def model_form_error_verify(primal, fine_primal, solver=None):
     """main_model_form_error_verify.cpp on one mesh.  `primal` and `fine_primal`: two solved PrimalDrivers, of the base and
     of the fine model, on the same mesh with the same local layout, objective, conditions and number of steps (else
     ValueError).  The objective must be linear in the state -- "Only valid for linear QoIs" (evaluations.hpp:105): average
-    displacement -- else ValueError.  Marches the adjoint of the fine model about the BASE history exactly as
+    displacement or a displacement component over an element set -- else ValueError.  Marches the adjoint of the fine model about the BASE history exactly as
     model_form_error does and calls error_contributions, exact_errors and linearization_errors (state = base step, fine =
     the fine run's step) with every step's z and phi.  Returns a ModelFormErrorVerify; the reference's test is
     |E_computed - E_exact| <= 1e-8 |E_exact| (+ allowance)."""
     torch, base, asm = primal.torch, primal.asm, fine_primal.asm
     _same_discretisation(base, asm)
-    if asm.objective[0] != "avg_disp":
-        raise ValueError("model_form_error_verify: only valid for linear QoIs (average displacement), not %r" % (asm.objective[0],))
+    linear = asm.objective[0] == "avg_disp" or asm.objective[:2] == ("subdomain", _l.C8_QOI_DISP_COMP)
+    if not linear:
+        raise ValueError("model_form_error_verify: only valid for linear QoIs (average displacement, displacement component), not %r" % (asm.objective[0],))
     if len(primal.u) != len(fine_primal.u):
         raise ValueError("model_form_error_verify: the two runs have %d and %d steps" % (len(primal.u) - 1, len(fine_primal.u) - 1))
     same = lambda a, b, k: len(a) == len(b) and all(np.array_equal(np.asarray(x[i]), np.asarray(y[i])) for x, y in zip(a, b) for i in range(k))

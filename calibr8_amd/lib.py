@@ -62,6 +62,18 @@ class CalibrationDesc(C.Structure):
                 ("dt_over_total_time", C.c_double)]
 
 
+class SubdomainQoiDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("elem_set", C.c_int32), ("index", C.c_int32)]
+
+
+class ReactionDesc(C.Structure):
+    _fields_ = [("coord_idx", C.c_int32), ("coord_value", C.c_double), ("coord_tol", C.c_double), ("reaction_comp", C.c_int32)]
+
+
+C8_QOI_AVG_STRESS, C8_QOI_AVG_LOCAL_VAR, C8_QOI_DISP_COMP = 0, 1, 2
+C8_QOI_KINDS = {"avg_stress": C8_QOI_AVG_STRESS, "avg_local_var": C8_QOI_AVG_LOCAL_VAR, "disp_comp": C8_QOI_DISP_COMP}
+
+
 class LbfgsOpts(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("grad_tol", C.c_double), ("step_tol", C.c_double),
                 ("max_ls_evals", C.c_int32), ("memory", C.c_int32)]
@@ -159,6 +171,8 @@ SYMBOLS = [
     ("c8_set_allreduce", C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p, C.c_int]),
     ("c8_set_qoi_avg_disp", C.c_int, [C.c_void_p]),
     ("c8_set_qoi_calibration", C.c_int, [C.c_void_p, C.POINTER(CalibrationDesc)]),
+    ("c8_set_qoi_subdomain", C.c_int, [C.c_void_p, C.POINTER(SubdomainQoiDesc)]),
+    ("c8_set_qoi_reaction", C.c_int, [C.c_void_p, C.POINTER(ReactionDesc)]),
     ("c8_set_measured", C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     ("c8_qoi_preprocess", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(C.c_double)]),
     ("c8_assemble_forward_jacobian", C.c_int, [C.c_void_p, C.POINTER(State), C.POINTER(System)]),

@@ -260,6 +260,30 @@ int c8_set_measured(c8_ctx* ctx, const double* u_meas, double load_meas);
 /* preprocess_qoi (evaluations.cpp:262-347); the adjoint entry points below run it themselves, this call only
  * reports: out (HOST, 3 doubles, may be NULL) = {side-set area, total load, load mismatch}. */
 int c8_qoi_preprocess(c8_ctx* ctx, const c8_state* st, double* out);
+/* Subdomain objectives (avg_stress.cpp, avg_local_var.cpp, disp_comp.cpp): the value of a load step is the sum over the
+ * elements of ONE element set and their local-state points of w dv q,
+ *   C8_QOI_AVG_STRESS      q = |dev_cauchy|, the Frobenius norm of the model's deviatoric Cauchy stress over its
+ *                              ndims x ndims block
+ *   C8_QOI_AVG_LOCAL_VAR   q = xi[index], `index` the flat position in the point's local state
+ *   C8_QOI_DISP_COMP       q = u[index] interpolated at the point
+ * Plain integrals: not divided by the volume, as in the reference.  The caller sums the steps; on a part of a multi-part
+ * mesh the sum covers the part's own elements and the caller sums the parts, as for "average displacement".
+ * Deliberate difference: |D| is not differentiable at D = 0, where the reference's derivative is NaN; here a point with
+ * |dev_cauchy| == 0 contributes value 0 and derivative 0.
+ * The adjoint kernels run with a zero objective; kernels of their own (c8_qoi_point.hip) add the value, subtract dJ/dxi
+ * from g before the adjoint Jacobian is assembled, subtract dJ/dx from b after it and add dJ/dp to the gradient, all in a
+ * fixed summation order (bitwise repeatable), on the context's stream.
+ * Returns C8_ERR_ARG for an element set, local dof or component out of range (C8_QOI_DISP_COMP: index >= c8_num_dims),
+ * C8_ERR_UNSUPPORTED for C8_QOI_AVG_LOCAL_VAR on a model without local state. */
+enum { C8_QOI_AVG_STRESS = 0, C8_QOI_AVG_LOCAL_VAR = 1, C8_QOI_DISP_COMP = 2 };
+typedef struct { int32_t kind, elem_set, index; } c8_subdomain_qoi_desc;   /* index: local dof k / component c / 0 */
+int c8_set_qoi_subdomain(c8_ctx* ctx, const c8_subdomain_qoi_desc* desc);
+/* Reaction (reaction.cpp without "compute torque"): the internal force component `reaction_comp` summed over the nodes
+ * with |x[coord_idx] - coord_value| < coord_tol -- out[1] of c8_qoi_preprocess.  The load term of "calibration" with no
+ * measured data and no face term: the adjoint kernels carry it themselves.  Multi-part meshes: the load is summed over
+ * the parts (c8_set_allreduce) and every part reports 1 / num_parts of it, so that the caller's sum counts it once. */
+typedef struct { int32_t coord_idx; double coord_value, coord_tol; int32_t reaction_comp; } c8_reaction_desc;
+int c8_set_qoi_reaction(c8_ctx* ctx, const c8_reaction_desc* desc);
 
 /* ---- the hot path (all array arguments are DEVICE pointers) --------------------------------- */
 /* eval_forward_jacobian (evaluations.cpp:12-154): R and dR/dx with the local state condensed;
