@@ -485,10 +485,10 @@ class Assembler:
 
     def vfm_forward_sens(self, u, p, u_prev, p_prev, xi_prev, xi, S_prev, S, ivw, divw):
         """eval_measured_residual_and_grad: as vfm_internal_power, S = local sensitivities [elems][pts][nloc][n_active]
-        from S_prev (None = 0), divw [n_active] += d(w^T R)/dp"""
+        from S_prev (None = 0), divw [n_active] += d(w^T R)/dp.  Without active parameters S may be None."""
         st = self._state(u, p, u_prev, p_prev, xi_prev, xi)
         return self._rc(self.L.c8_vfm_forward_sens(self.h, C.byref(st), None if S_prev is None else C.c_void_p(S_prev.data_ptr()),
-                                                   C.c_void_p(S.data_ptr()), C.c_void_p(ivw.data_ptr()),
+                                                   None if S is None else C.c_void_p(S.data_ptr()), C.c_void_p(ivw.data_ptr()),
                                                    C.c_void_p(divw.data_ptr())))
 
     def vfm_adjoint_step(self, u, p, u_prev, p_prev, xi_prev, xi, c, h, grad):

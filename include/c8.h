@@ -384,7 +384,8 @@ int c8_vfm_internal_power(c8_ctx* ctx, const c8_state* st, double* b, double* iv
  * (virtual_power.cpp:141-186): as c8_vfm_internal_power, and the local sensitivities
  * S = -(dC/dxi)^-1 (dC/dp + dC/dxi_prev S_prev), divw[c8_num_active_params] += [(dR/dxi)^T w]^T S + (dR/dp)^T w.
  * S, S_prev: [elems][points][local dofs][c8_num_active_params] (column = position of the parameter in grad);
- * S_prev NULL = 0 (first step). */
+ * S_prev NULL = 0 (first step).  An element writes, and reads of S_prev, only the columns of its own element set's
+ * parameters: the other columns of its rows keep what S held before the call.  Without active parameters S may be NULL. */
 int c8_vfm_forward_sens(c8_ctx* ctx, const c8_state* st, const double* S_prev, double* S, double* ivw, double* divw);
 /* eval_vfm_adjoint_gradient (evaluations.cpp:1975-2143) at the stored state of step n, c = the step's scaled mismatch:
  * phi = (dC/dxi)^-T (-c (dR/dxi)^T w - h), h <- (dC/dxi_prev)^T phi (in place, [elems][points][local dofs], zero
