@@ -17,29 +17,29 @@ def harness(tmp_path_factory):
     return ec.build_harness(tmp_path_factory.mktemp("c8_error_host"))
 
 
-def one_element_oracle(cs, e):
-    """an oracle context on the one-element mesh of element e: its nodes, the case's parameters"""
+def one_element_oracle(cs, e, **kw):
+    """an oracle context on the one-element mesh of element e: its nodes, the case's parameters (kw: oracle settings)"""
     nodes = cs.conn[e]
     c1, conn1 = np.ascontiguousarray(cs.c[nodes]), np.arange(len(nodes), dtype=np.int32).reshape(1, -1)
     if cs.model == cc.HYBRID:
         import hybrid_cases as hc
-        return hc.hybrid_oracle((cs.et, c1, conn1), hc.NETS[cc.HYBRID_NET])[0]
-    return ol.Oracle(cs.et, c1, conn1, cs.model, cs.params)
+        return hc.hybrid_oracle((cs.et, c1, conn1), hc.NETS[cc.HYBRID_NET], **kw)[0]
+    return ol.Oracle(cs.et, c1, conn1, cs.model, cs.params, **kw)
 
 
-@pytest.mark.parametrize("rid", cc.ROW_IDS)
-def test_E_R_is_z_dot_the_oracles_element_residual(harness, rid):
-    """E_R[e] = z_e . b_e with b_e the oracle's global residual on the one-element mesh of e, to 1e-12 of sum |z_i b_i|"""
+def check_E_R_against_element_residuals(harness, rid, stab_mult=1.0):
+    """E_R[e] = z_e . b_e with b_e the oracle's global residual on the one-element mesh of e, to 1e-12 of sum |z_i b_i|;
+    returns E_R"""
     cs = cc.case(rid)
     plastic, elastic = cs.branches()
     if cs.model not in cc.NO_PLASTICITY:
         assert plastic > 0 and elastic > 0, (rid, plastic, elastic)
     z_u, z_p, phi = ec.adjoints(cs)
-    E_R, _ = ec.case_host(harness, cs, z_u, z_p, phi)
+    E_R, _ = ec.host_error(harness, cs.et, cs.c, cs.conn, cs.model, cs.params, *cs.state, z_u, z_p, phi, nn=cs.nn, stab_mult=stab_mult)
     nd = cs.orc.ndims
     worst = 0.0
     for e, nodes in enumerate(cs.conn):
-        orc = one_element_oracle(cs, e)
+        orc = one_element_oracle(cs, e, stab_mult=stab_mult)
         loc = lambda a, w: np.ascontiguousarray(np.asarray(a).reshape(-1, w)[nodes].ravel())
         ls = orc.new_linsys()
         orc.global_residual(loc(cs.u, nd), loc(cs.p, 1), loc(cs.u_prev, nd), loc(cs.p_prev, 1), np.ascontiguousarray(cs.xi_prev[e:e + 1]),
@@ -49,6 +49,23 @@ def test_E_R_is_z_dot_the_oracles_element_residual(harness, rid):
         assert scale > 0 and abs(E_R[e] - ref) < 1e-12 * scale, (rid, e, E_R[e], ref, scale)
         worst = max(worst, abs(E_R[e] - ref) / scale)
     print("%s: worst |E_R - z.b| / sum|z_i b_i| = %.2e over %d elements" % (rid, worst, len(cs.conn)))
+    return E_R
+
+
+@pytest.mark.parametrize("rid", cc.ROW_IDS)
+def test_E_R_is_z_dot_the_oracles_element_residual(harness, rid):
+    """E_R[e] = z_e . b_e with b_e the oracle's global residual on the one-element mesh of e, to 1e-12 of sum |z_i b_i|"""
+    check_E_R_against_element_residuals(harness, rid)
+
+
+@pytest.mark.parametrize("rid", ["small_J2-hex8", "hyper_J2-tet4", "hyper_J2_plane_strain-tri3"])
+def test_E_R_follows_the_stabilization_multiplier(harness, rid):
+    """the same with stab_mult = 3.7 in the harness and in the oracle (settings_cases.STAB); E_R moves with the multiplier by
+    more than 1e-5 of its largest entry, seven orders above the bar (the stabilisation term is one of many in z . R)"""
+    E_R = check_E_R_against_element_residuals(harness, rid, stab_mult=3.7)
+    cs = cc.case(rid)
+    one, _ = ec.case_host(harness, cs, *ec.adjoints(cs))
+    assert np.abs(E_R - one).max() > 1e-5 * np.abs(one).max()
 
 
 @pytest.mark.parametrize("rid", cc.ROW_IDS)

@@ -58,16 +58,24 @@ def test_shape_partition_of_unity_and_gradients():
         assert np.abs(dN.T @ (X @ a) - a).max() < 1e-12
 
 
-@pytest.mark.parametrize("model,params,eps", [("small_J2", J2, 0.004), ("small_J2", J2, 0.001),
-                                              ("elastic", [1000.0, 0.25, 1e-3, 10.0], 0.002),
-                                              ("hyper_J2", [1000.0, 0.25, 2.0, 1.0, 5.0, 0.5, 0.5, 100.0], 0.004),
-                                              ("small_hill", [1000.0, 0.25, 2.0, 1.0, 1.1, 0.9, 1.05, 0.95, 1.0, 1.0, 50.0], 0.004),
-                                              ("isotropic_elastic", [1000.0, 0.25], 0.002),
-                                              ("hypo_hill", [1000.0, 0.25, 2.0, 1.0, 1.1, 0.9, 1.05, 0.95, 1.0, 1.0, 50.0], 0.004)])
-def test_jacobian_matches_finite_differences_hex8(model, params, eps):
+FD_CASES = [("small_J2", J2, 0.004), ("small_J2", J2, 0.001),
+            ("elastic", [1000.0, 0.25, 1e-3, 10.0], 0.002),
+            ("hyper_J2", [1000.0, 0.25, 2.0, 1.0, 5.0, 0.5, 0.5, 100.0], 0.004),
+            ("small_hill", [1000.0, 0.25, 2.0, 1.0, 1.1, 0.9, 1.05, 0.95, 1.0, 1.0, 50.0], 0.004),
+            ("isotropic_elastic", [1000.0, 0.25], 0.002),
+            ("hypo_hill", [1000.0, 0.25, 2.0, 1.0, 1.1, 0.9, 1.05, 0.95, 1.0, 1.0, 50.0], 0.004)]
+STAB = (0.37, 1.0, 3.7)  # stabilization multipliers of the checks below (settings_cases.STAB and the default)
+
+
+# every case at the default stabilization multiplier, and the finite-deformation model (whose A10 carries the multiplier as
+# well as A11) once more at 3.7
+@pytest.mark.parametrize("model,params,eps,stab_mult",
+                         [pytest.param(*cs, 1.0, id="%s-params%d-%g" % (cs[0], k, cs[2])) for k, cs in enumerate(FD_CASES)] +
+                         [pytest.param(*FD_CASES[3], STAB[2], id="%s-params3-%g-stab%g" % (FD_CASES[3][0], FD_CASES[3][2], STAB[2]))])
+def test_jacobian_matches_finite_differences_hex8(model, params, eps, stab_mult):
     c, conn, sets = brick(3, 2, 2, 1.0, 0.8, 0.7)
     c = jiggle(c, sets, 0.05)
-    be = ol.Oracle(ol.HEX8, c, conn, model, params)
+    be = ol.Oracle(ol.HEX8, c, conn, model, params, stab_mult=stab_mult)
     u, p = prescribed_fields(c, eps, ramp=True, perturb=5e-2)
     u0, p0 = np.zeros_like(u), np.zeros_like(p)
     xi_prev = be.new_state()
@@ -95,6 +103,35 @@ def test_jacobian_matches_finite_differences_hex8(model, params, eps):
         fd = (Rp - Rm) / (2 * h)
         worst = max(worst, np.abs(A @ v - fd).max() / np.abs(A @ v).max())
     assert worst < 2e-6, worst
+
+
+@pytest.mark.parametrize("model,params", [(FD_CASES[0][0], FD_CASES[0][1]), (FD_CASES[3][0], FD_CASES[3][1])], ids=["small_J2", "hyper_J2"])
+def test_system_is_affine_in_the_stabilization_multiplier(model, params):
+    """at a fixed state the pressure residual b[1] and the blocks A10, A11 are affine in stab_mult (the stabilisation term is
+    tau = stab_mult h^2 / (2 mu) times a function of the state): value(3.7) - value(0.37) = (3.7 - 0.37) / (1 - 0.37) (value(1) -
+    value(0.37)) to 1e-13 of the largest entry; the local state, b[0], A00 and A01 do not depend on it, bit for bit"""
+    c, conn, sets = brick(3, 2, 2, 1.0, 0.8, 0.7)
+    c = jiggle(c, sets, 0.05)
+    u, p = prescribed_fields(c, 0.004, ramp=True, perturb=5e-2)
+    u0, p0 = np.zeros_like(u), np.zeros_like(p)
+    out = {}
+    for s in STAB:
+        be = ol.Oracle(ol.HEX8, c, conn, model, params, stab_mult=s)
+        ls, xi = be.new_linsys(), be.new_state()
+        assert be.forward_jacobian(u, p, u0, p0, be.new_state(), xi, ls) == 0
+        out[s] = {"xi": xi, "b0": ls.b[0], "b1": ls.b[1], "A00": ls.A[0][0], "A01": ls.A[0][1], "A10": ls.A[1][0], "A11": ls.A[1][1]}
+    lo, one, hi = (out[s] for s in STAB)
+    assert (one["xi"][:, :, -1] > 0).any() and (one["xi"][:, :, -1] == 0).any()
+    for k in ("xi", "b0", "A00", "A01"):
+        assert np.array_equal(lo[k], one[k]) and np.array_equal(hi[k], one[k]), k
+    ratio = (STAB[2] - STAB[0]) / (STAB[1] - STAB[0])
+    for k in ("b1", "A10", "A11"):
+        top = max(np.abs(v[k]).max() for v in (lo, one, hi))
+        assert np.abs((hi[k] - lo[k]) - ratio * (one[k] - lo[k])).max() <= 1e-13 * top, k
+        if k != "A10" or model == "hyper_J2":  # A10 of a small-strain model has no stabilisation term
+            assert np.abs(hi[k] - lo[k]).max() > 1e-3 * top, k
+        else:
+            assert np.array_equal(hi[k], lo[k])
 
 
 def test_patch_test_hex8_elastic():
