@@ -72,6 +72,27 @@ template <class Lane> struct GpuExec {
     bool const upper = (k & 8) != 0;
     return __hiloint2double(upper ? b_hi : a_hi, upper ? b_lo : a_lo);
   }
+  // get(l) of lane l ^ C, C = 1 .. 7, inside the caller's group of 8 lanes (lane_xor8, c8_assemble_node.hpp): every lane
+  // evaluates get for itself and v_mov_b32 DPP exchanges both halves of the double -- quad_perm for C = 1, 2, 3,
+  // row_half_mirror (lane i of a half row takes lane 7 - i = i ^ 7) for C = 7, the mirror followed by the quad_perm of
+  // C ^ 7 for C = 4, 5, 6.  No LDS, no barrier.  A disabled source lane would leave the reader its own value: a group of 8
+  // lanes must be active or inactive as a whole wherever this is used.
+  using has_xor8 = void;
+  template <int C, class F> __device__ __forceinline__ double xor8(int lane, F get) {
+    static_assert(C >= 1 && C <= 7, "partner inside the group of 8 lanes");
+    constexpr int Q = C < 4 ? C : C ^ 7, QP = Q == 1 ? 0xB1 : (Q == 2 ? 0x4E : 0x1B);  // quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0]
+    double const x = get(lane);
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    if constexpr (C >= 4) {
+      lo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xf, 0xf, false);  // row_half_mirror
+      hi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xf, 0xf, false);
+    }
+    if constexpr (C != 7) {
+      lo = __builtin_amdgcn_update_dpp(lo, lo, QP, 0xf, 0xf, false);
+      hi = __builtin_amdgcn_update_dpp(hi, hi, QP, 0xf, 0xf, false);
+    }
+    return __hiloint2double(hi, lo);
+  }
   // get(l) of lane l ^ 32 (the other half of the wavefront)
   template <class F> __device__ __forceinline__ double xor32(int lane, F get) { return __shfl_xor(get(lane), 32); }
   // lanes 0..31: getA(lane) + getA(lane + 32); lanes 32..63: getB(lane - 32) + getB(lane).  v_permlane32_swap (gfx950)
@@ -468,7 +489,10 @@ template <class E> static hipError_t launch_gather_rows(GatherArgs const& ga, in
 // 3.68 / 4.51 ms beside 4.18 / 5.21 ms of those in one call (profiles/README.md, jinv_*).  They also issue phase
 // A2's table and state loads beside the connectivity and two of phase B's first rows under the closed form (same loads, same
 // bits, one dependent round trip earlier each): 3.54 / 4.35 ms beside 3.61 / 4.44 ms in one call (last part;
-// profiles/README.md, chain_*).
+// profiles/README.md, chain_*).  Phase B no longer walks the dN/dx table: a column node's gradient is formed from the inverse
+// Jacobian by the lane that holds it and handed over by GpuExec::xor8 (16 vector-memory instructions and 24 eight-byte units per
+// lane and node less, 60 DPP moves and about 110 vector-ALU instructions more): 3.31-3.33 / 3.78-3.79 ms beside 3.62-3.63 /
+// 4.46 ms in one call (last part; profiles/README.md, xlane_*).
 #ifndef C8_NODE_WAVES
 #define C8_NODE_WAVES 3
 #endif

@@ -14,29 +14,26 @@
 // block of the element matrix is formed exactly once, by the wavefront of its row node.
 //
 //   top      lane = pattern         forward assembly: the eight shape values of the reference element at its points into LDS
-//            (nshape, hex_pattern): the row node reads its N_a there instead of forming it
+//            (nshape, hex_pattern): phase B and the row node read them instead of forming them at every step
 //   phase A  lane = (element s of the node, point)      interpolate the point quantities from the element's nodal
 //            values -- their gradients in the reference element first, then the point's cached inverse Jacobian (nine
 //            coalesced loads) --, closed form (radial return, consistent tangent), the row node's record of the point into
 //            LDS, the point's share of the node's residual; the lane of the element's local node 0 stores the converged
 //            local state.  The loads of a phase are issued one dependent round trip ahead of it where they depend on the
-//            element alone (NodeLane): the point's inverse Jacobian, previous state and weights beside the connectivity.
-//            Lane l of an element owns point hex_code(l), not point l (phase B, below); the eight lanes still read 64
-//            contiguous bytes per load, and per point nothing changes
+//            element alone (NodeLane): the point's inverse Jacobian, previous state and weights beside the connectivity, the
+//            first rows phase B reads under the closed form
 //   phase B  lane = (element s of the node, column node m)   the 4 x 4 block d R_(node,.) / d x_(m,.) summed over the
-//            element's eight points: 16 accumulators.  No load and no table: dN_m/dx at a point is G(pt)^T dN_m/dxi(pt); the
-//            lane that holds G(pt) since phase A forms it for the lane that needs it at that step, and a register exchange
-//            inside the group of eight lanes (lane_xor8: DPP moves on the GPU) delivers the three doubles.  With the points
-//            owned as above, step c pairs lane l with lane l ^ c and the reference gradient is a constant of the step
+//            element's eight points: 16 accumulators
 //   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order.  The
 //            accumulator is an IMAGE of the node's four CSR row blocks, entry for entry in their order (NodeShared::img*)
 //   phase D  the finished rows added to (or assigned to) the four CSR blocks -- four straight copies, lane j + 64 it
 //            takes entry j + 64 it of a block -- the residual entries to b
 //
+// In the walk over the skewed shape table (phase B) a lane keeps ONE rotating byte offset, (off + 8) & 56, and derives every
+// address of a step from it by a shift: the table's two columns, the record, nshape.
+//
 // Requires an element with 8 nodes, 8 coupled points and identical point sets for both ip sets (hex8), the cached
-// shape tables (c8_set_shape_cache: of an element's entry these kernels read the inverse Jacobians, the weights and the size,
-// not the dN/dx section), xi != xi_prev (an element's previous state is read by eight wavefronts), and an executor whose
-// groups of eight lanes are active or inactive as a whole wherever lane_xor8 is called (NodeLane::valid is per element).
+// shape tables (c8_set_shape_cache) and xi != xi_prev (an element's previous state is read by eight wavefronts).
 #pragma once
 
 #include "c8_assemble_wave.hpp"
@@ -86,11 +83,17 @@ template <class E, class ModelD, int MAXDEG, bool MANY> struct NodeShared {
 // the double at BYTE offset off (a multiple of 8) from p
 C8_HD double const* at_byte(double const* p, int off) { return reinterpret_cast<double const*>(reinterpret_cast<char const*>(p) + off); }
 
-// Loads issued one phase ahead of their use and carried in the lane record: lane (s, m) of phase A1 is lane (s, point
-// hex_code(m)) of phase A2 and lane (s, column node m) of phase B, so a lane issues its own later loads as soon as it knows
-// its element.  G stays in the record through phase B, each row times the point's sign along that axis: the lanes of the
-// element form their column nodes' dN/dx from it (lane_xor8)
+#ifndef C8_TUNE_NODE_HAHEAD
+#define C8_TUNE_NODE_HAHEAD 3
+#endif
+
+// Loads issued one phase ahead of their use and carried in the lane record: lane (s, m) of phase A1 is lane (s, point m) of
+// phase A2 and lane (s, column node m) of phase B, so a lane issues its own later loads as soon as it knows its element.
+// NODE_HQ_EARLY: rows of the skewed dN/dx table fetched under the closed form for phase B (the third row of the look-ahead
+// takes the forward kernel from 124 to 129 registers, three wavefronts per SIMD instead of four: slower)
 constexpr int NODE_NXI = 7;  // entries of the local state a lane carries (small_J2)
+constexpr int NODE_HQ_EARLY = 2;
+static_assert(NODE_HQ_EARLY <= C8_TUNE_NODE_HAHEAD, "the rows fetched early are rows of phase B's look-ahead");
 template <int MAXDEG> struct NodeLane {
   static constexpr int N00 = (9 * MAXDEG + 63) / 64, N01 = (3 * MAXDEG + 63) / 64;
   double J[16];
@@ -98,33 +101,10 @@ template <int MAXDEG> struct NodeLane {
   double bold;                               // ... and of its residual entry (lanes 0..3)
   double rs;
   double G[9], xo[NODE_NXI], w, h;           // A1 -> A2: the point's inverse Jacobian, previous state (forward), weight; the element's size
-                                             // A2 -> B: G, row k times the point's sign along k
+  double hq[NODE_HQ_EARLY][3];               // A2 -> B: the column node's dN/dx at the first steps of phase B
   int e, a, pos;
   bool valid;
 };
-
-// get(l ^ C), C = 1 .. 7: the value of get at the partner lane inside the caller's group of eight lanes (phase B: the lanes of
-// one element).  get(l) may read only what lane l's record (ex.lane(l)) held before the phase began.  An executor with a
-// register exchange provides xor8<C>(lane, get) (the GPU's: DPP moves, every lane evaluates get for itself and the values
-// change places); one without it addresses every lane's record, and get is evaluated for the partner -- with the marker `cur`
-// of an executor that watches which lane's record is touched (the CPU emulation) moved to the partner for the call.
-// A group of eight lanes is valid or invalid as a whole (NodeLane::valid), so no exchange reaches into an inactive group.
-template <class EX, class = void> struct has_xor8 : std::false_type {};
-template <class EX> struct has_xor8<EX, std::void_t<typename EX::has_xor8>> : std::true_type {};
-template <class EX, class = void> struct has_lane_marker : std::false_type {};
-template <class EX> struct has_lane_marker<EX, std::void_t<decltype(std::declval<EX&>().cur)>> : std::true_type {};
-template <int C, class EX, class F> C8_HD double lane_xor8(EX& ex, int lane, F get) {
-  static_assert(C >= 0 && C < 8, "partner inside the group of eight lanes");
-  if constexpr (C == 0) return get(lane);
-  else if constexpr (has_xor8<EX>::value) return ex.template xor8<C>(lane, get);
-  else if constexpr (has_lane_marker<EX>::value) {
-    int const saved = ex.cur;
-    ex.cur = lane ^ C;
-    double const v = get(lane ^ C);
-    ex.cur = saved;
-    return v;
-  } else return get(lane ^ C);
-}
 
 // The reference hex8 at its Gauss points BY AGREEMENT PATTERN.  Node signs and point coordinates are +-1 and +-1/sqrt(3) per
 // axis, so N_m and dN_m/dxi at a point depend only on the set j of axes on which the node's sign equals the point's (bit k of
@@ -144,13 +124,13 @@ template <class E> C8_HD void hex_pattern(int j, double* v) {
 }
 
 // shape values of the reference hex8 at its Gauss points: E::N(n, xi) operation for operation, 0.125 (1 + sx xi_0)
-// (1 + sy xi_1) (1 + sz xi_2), with the point fixed per lane and the node a lane value; signs are selected as values (no
-// indexed tables: they would live in scratch).
-// Adjoint assembly only, for N_a of the row node (the forward assembly reads NodeShared::nshape; with that table K3 measured
-// 2.5-3.4 % SLOWER).  The signs are +-1, so 1 + s * xi is exact in the product, and the factors are multiplied in
-// the order of hex_pattern: the same bits.
+// (1 + sy xi_1) (1 + sz xi_2), with either the point (of_point) or the node (of_node) fixed per lane and the other index a
+// lane value; signs are selected as values (no indexed tables: they would live in scratch).
+// Adjoint assembly only (the forward assembly reads NodeShared::nshape): formed at every step; with a table of the values in
+// LDS K3 measured 2.5-3.4 % SLOWER.  The signs are +-1, so 1 + s * xi is exact in the product whichever index
+// is fixed, and the factors are multiplied in the same order -- at_node and at_point give the same bits.
 template <class E> struct HexShape {
-  double c[3];  // the point's coordinates
+  double c[3];  // of_point: the point's coordinates; of_node: the node's signs
   C8_HD static HexShape of_point(int pt) {
     double w;
     HexShape h;
@@ -160,6 +140,16 @@ template <class E> struct HexShape {
   C8_HD double at_node(int n) const {
     double const sx = ((n ^ (n >> 1)) & 1) ? 1. : -1., sy = ((n >> 1) & 1) ? 1. : -1., sz = ((n >> 2) & 1) ? 1. : -1.;  // E::sign
     return 0.125 * (1. + sx * c[0]) * (1. + sy * c[1]) * (1. + sz * c[2]);
+  }
+  C8_HD static HexShape of_node(int n) {
+    HexShape h;
+    E::sign(n, h.c[0], h.c[1], h.c[2]);
+    return h;
+  }
+  C8_HD double at_point(int pt) const {
+    double xi[3], w;
+    E::point(0, pt, xi, w);
+    return 0.125 * (1. + c[0] * xi[0]) * (1. + c[1] * xi[1]) * (1. + c[2] * xi[2]);
   }
 };
 
@@ -213,7 +203,7 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     //      loads and their registers) ------------------------------------------------------------------------------------
     ex.each([&](int lane) {
       auto& r = ex.lane(lane);
-      int const s = lane >> 3, m = lane & 7, mp = hex_code(m);  // mp: the point this lane owns in phase A2
+      int const s = lane >> 3, m = lane & 7;
       r.valid = s < ne;
       r.rs = 0.;
       if (!r.valid) return;
@@ -230,13 +220,13 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       {
         double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
         C8_UNROLL
-        for (int c = 0; c < 9; ++c) r.G[c] = t[SHAPE_JINV + 8 * c + mp];
+        for (int c = 0; c < 9; ++c) r.G[c] = t[SHAPE_JINV + 8 * c + m];
         if constexpr (!ADJ) {
-          size_t const q0 = ((size_t)e * E::NP0 + mp) * NL;
+          size_t const q0 = ((size_t)e * E::NP0 + m) * NL;
           C8_UNROLL
           for (int j = 0; j < NL; ++j) r.xo[j] = fa.xi_prev[q0 + j];
         }
-        r.w = t[SHAPE_WDV + mp];
+        r.w = t[SHAPE_WDV + m];
         r.h = t[SHAPE_H];
       }
       double* const nv = sh.nodal[s][m];
@@ -249,9 +239,10 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       auto& r = ex.lane(lane_);
       int lane = lane_;
       C8_PIN(lane);  // the offsets below are formed here, not at the top of the kernel and kept in registers
-      int const s = lane >> 3, pt = hex_code(lane & 7);  // lane l of an element owns point hex_code(l): phase B, below
+      int const s = lane >> 3, pt = lane & 7;
       if (!r.valid) return;
       int const e = r.e, a = r.a;
+      double const* const t = mt.shape + (size_t)e * SHAPE_STRIDE;
       size_t const q0 = ((size_t)e * E::NP0 + pt) * NL;
       // the point's inverse Jacobian G[3 k + d] = d xi_k / d x_d (the eight lanes of an element read 64 contiguous bytes per
       // component) and, forward, its previous state: fetched by this lane in phase A1
@@ -320,10 +311,9 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
         for (int j = 0; j < NL; ++j) xi_old[j] = fa.xi_prev[q0 + j];
       }
       int const es = mt.elem_set ? mt.elem_set[e] : 0;
-      // phase B's operand of this lane as the holder of G(pt): G with row k times the sign of the point along k, which is
-      // the sign of node (lane & 7) along k (exact).  In the record: the lanes of the element read it there (lane_xor8)
+      // phase B's first rows of the skewed dN/dx table for this lane as column node pt, fetched under the closed form
       C8_UNROLL
-      for (int c = 0; c < 9; ++c) r.G[c] = ((pt >> (c / 3)) & 1) ? G[c] : -G[c];
+      for (int k = 0; k < NODE_HQ_EARLY; ++k) { r.hq[k][0] = t[k * 24 + pt * 2 + 0]; r.hq[k][1] = t[k * 24 + pt * 2 + 1]; r.hq[k][2] = t[k * 24 + 16 + pt]; }
       typename Model::ClosedForm cf;
       Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, r.h, ms.stab_mult, cf, true);
       if (!ADJ && a == 0) {  // local->scatter (local_residual.cpp:624-631): once per element, by the wavefront of its first node
@@ -377,35 +367,45 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       for (int j = 0; j < 16; ++j) r.J[j] = 0.;
       if (!r.valid) return;
       int const s = lane >> 3, m = lane & 7;
+      double const* const t = mt.shape + (size_t)r.e * SHAPE_STRIDE;
       double const el[2] = {sh.el[s][0], sh.el[s][1]};
-      // dN_m/dx of this lane's column node from the inverse Jacobians the element's lanes hold since phase A2, no table.  At
-      // step c the lane takes the point of lane l ^ c, pt = hex_code(l) ^ hex_code(c): node m = l agrees with that point on
-      // the axes hex_code(c) ^ 7 -- the same pattern in every lane, so N_m(pt) and |dN_m/dxi_k| are constants of the step.
-      // The HOLDER of G(pt) forms h = G^T dN_m'/dxi for its asker m' = l ^ c: the asker's sign along k is the holder's own
-      // (in NodeLane::G since A2) times the step's flip, bit k of hex_code(c); nine operations, then a lane exchange
-      auto step = [&](auto cc) {
-        constexpr int c = decltype(cc)::value, hc = hex_code(c);
-        double v[4];
-        hex_pattern<E>(hc ^ 7, v);
-        double const k0 = (hc & 1) ? -v[1] : v[1], k1 = (hc & 2) ? -v[2] : v[2], k2 = (hc & 4) ? -v[3] : v[3];
-        double h[3];
-        C8_UNROLL
-        for (int d = 0; d < 3; ++d)
-          h[d] = lane_xor8<c>(ex, lane, [&](int l) -> double {
-            double const* const Gs = ex.lane(l).G;
-            return k0 * Gs[d] + k1 * Gs[3 + d] + k2 * Gs[6 + d];
-          });
-        Model::closed_form_block(sh.rec(s, hex_code(m) ^ hc), el, h, v[0], r.J);
+      HexShape<E> Nn;  // adjoint only
+      if constexpr (ADJ) Nn = HexShape<E>::of_node(m);
+      // dN_m/dx of this lane's column node: at step i the element's eight lanes read row i of the skewed table, this lane
+      // the entry of point (i - m) mod 8; C8_TUNE_NODE_HAHEAD steps ahead of the arithmetic, the first NODE_HQ_EARLY rows
+      // fetched in phase A2.  off = 8 pt rotates from step to step; multiplied, it addresses the point's record and the
+      // node's shape value at the point
+      constexpr int AH = C8_TUNE_NODE_HAHEAD;
+      double hq[AH + 1][3];
+      C8_UNROLL
+      for (int k = 0; k < AH; ++k) {
+        if (k < NODE_HQ_EARLY) { hq[k][0] = r.hq[k][0]; hq[k][1] = r.hq[k][1]; hq[k][2] = r.hq[k][2]; }
+        else { hq[k][0] = t[k * 24 + m * 2 + 0]; hq[k][1] = t[k * 24 + m * 2 + 1]; hq[k][2] = t[k * 24 + 16 + m]; }
+      }
+      int off = ((0 - m) & 7) * 8;
+      int const cm8 = (hex_code(m) ^ 7) * 8;  // forward: off ^ cm8 is the byte offset of N_m at point off / 8 in nshape
+      C8_UNROLL
+      for (int i = 0; i < E::NP0; ++i) {
+        hq[AH][0] = hq[AH][1] = hq[AH][2] = 0.;
+        if (i + AH < E::NP0) {
+          hq[AH][0] = t[(i + AH) * 24 + m * 2 + 0];
+          hq[AH][1] = t[(i + AH) * 24 + m * 2 + 1];
+          hq[AH][2] = t[(i + AH) * 24 + 16 + m];
+        }
+        double const hc[3] = {hq[0][0], hq[0][1], hq[0][2]};
+        double Nm;
+        if constexpr (ADJ) Nm = Nn.at_point(off >> 3);
+        else Nm = *at_byte(sh.nshape, off ^ cm8);
+        Model::closed_form_block(at_byte(sh.rec(s, 0), SH::LDR * off), el, hc, Nm, r.J);
+        off = (off + 8) & 56;
         // one point's record in registers at a time: without the lines below the compiler fetches the records of all
         // eight points first (over a hundred doubles) and spills
         C8_UNROLL
         for (int j = 0; j < 16; ++j) C8_PIN(r.J[j]);
         C8_SCHED_FENCE();
-      };
-      step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{});
-      step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 3>{});
-      step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-      step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{});
+        C8_UNROLL
+        for (int k = 0; k < AH; ++k) { hq[k][0] = hq[k + 1][0]; hq[k][1] = hq[k + 1][1]; hq[k][2] = hq[k + 1][2]; }
+      }
       if (m < 4) {
         double v = 0.;
         C8_UNROLL
