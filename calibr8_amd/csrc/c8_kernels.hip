@@ -492,7 +492,11 @@ template <class E> static hipError_t launch_gather_rows(GatherArgs const& ga, in
 // profiles/README.md, chain_*).  Phase B no longer walks the dN/dx table: a column node's gradient is formed from the inverse
 // Jacobian by the lane that holds it and handed over by GpuExec::xor8 (16 vector-memory instructions and 24 eight-byte units per
 // lane and node less, 60 DPP moves and about 110 vector-ALU instructions more): 3.31-3.33 / 3.78-3.79 ms beside 3.62-3.63 /
-// 4.46 ms in one call (last part; profiles/README.md, xlane_*).
+// 4.46 ms in one call (profiles/README.md, xlane_*).  Phase B now sums over an element's points first and
+// combines the terms of the block once, after the eighth point (Model::closed_form_block_sums / _finish: 41 operations per
+// step and 24 at the end instead of 59 per step; 111 of 868 FP64 instructions less in K1, 128 registers, four wavefronts
+// per SIMD as before): 3.15-3.16 / 3.65-3.66 ms beside 3.35-3.36 / 3.79-3.82 ms in one call (last part;
+// profiles/README.md, sums_*).
 #ifndef C8_NODE_WAVES
 #define C8_NODE_WAVES 3
 #endif

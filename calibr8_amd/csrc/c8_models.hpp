@@ -326,7 +326,8 @@ template <class T, int DIM> struct SmallJ2Dim {
   //   (u_i, u_k)  w [ delta_ik a/2 (g.h) + a/2 g_k h_i - a/3 g_i h_k + b (n g)_i (n' h)_k ],   n' = n - tr(n)/3 I
   //   (u_i, p)   -w g_i N_m        (p, u_k)  -w N_a h_k        (p, p)  -w N_a N_m / kappa - tau w (g.h)
   // closed_form_row gathers what depends on the point and the ROW node only (NROW doubles), closed_form_block adds the block
-  // of one column node: 57 operations per point and node pair, no selects.
+  // of one column node: 59 operations per point and node pair, no selects.  The row-per-node kernels sum over the points
+  // first and combine afterwards (closed_form_block_sums / closed_form_block_finish below: 41 per point, 24 once per pair).
   static constexpr bool HAS_CLOSED_FORM_ROWS = HAS_CLOSED_FORM;
   static constexpr int NROW = 14;
   // r: w g (3) | w b (n g) (3) | a/2 | w N_a | n' (xx xy xz yy yz zz);   el (the same at every point of an element): tau, 1/kappa
@@ -512,6 +513,65 @@ template <class T, int DIM> struct SmallJ2Dim {
     C8_UNROLL
     for (int k = 0; k < 3; ++k) J[12 + k] = fma(-r[7], h[k], J[12 + k]);
     J[15] = fma(-el[0], gh, fma(-(r[7] * el[1]), Nm, J[15]));
+  }
+  // The same block with the combination of the three "a" terms taken ONCE, after the sum over the points (the row-per-node
+  // kernels; closed_form_block above stays for the source frozen in tests/emul/).  With p1 = a/2 w g (a inside the sum: it
+  // differs from point to point where points are plastic) and X_ki = sum_pt p1_k h_i,
+  //   sum_pt w [ delta_ik a/2 (g.h) + a/2 g_k h_i - a/3 g_i h_k ] = X_ki - 2/3 X_ik + delta_ik tr X,
+  // so a point adds to X and to C_ik = sum_pt w b (n g)_i (n' h)_k only: 41 operations per point and node pair in
+  // closed_form_block_sums, 24 once per pair in closed_form_block_finish (closed_form_block: 59 per point).
+  // S: C (3 i + k) | X (9 + 3 k + i) | (u_i, p) 18.. | (p, u_k) 21.. | Q = sum_pt [ w N_a N_m + rho w (g.h) ], rho = tau kappa,
+  // which closes as (p, p) = -Q / kappa: one scalar of the element is live through the sum, not two.
+  static constexpr int NSUM = 25;
+  // The element's scalars the two functions below take, from what closed_form left (t): rho = tau kappa, 1/kappa.  kappa as
+  // closed_form forms it, operation for operation: called next to it, the compiler forms it once
+  C8_HD static void closed_form_block_scalars(double const* prm, double const* t, double* es) {
+    double const kappa = prm[0] * c8_rcp(3. * (1. - 2. * prm[1]));
+    es[0] = t[4] * kappa;
+    es[1] = t[3];
+  }
+  // FIRST: the sums START with this point (assigned, not added to zero: a zero may come out as -0 where 0 + x gives +0)
+  template <bool FIRST = false>
+  C8_HD static void closed_form_block_sums(double const* r, double rho, double const* h, double Nm, double* S) {
+    double const gh = r[0] * h[0] + r[1] * h[1] + r[2] * h[2];
+    double const nh[3] = {r[8] * h[0] + r[9] * h[1] + r[10] * h[2], r[9] * h[0] + r[11] * h[1] + r[12] * h[2],
+                          r[10] * h[0] + r[12] * h[1] + r[13] * h[2]};
+    double const p1[3] = {r[6] * r[0], r[6] * r[1], r[6] * r[2]};   // a/2 w g_k
+    if constexpr (FIRST) {
+      C8_UNROLL
+      for (int i = 0; i < 3; ++i)
+        C8_UNROLL
+        for (int k = 0; k < 3; ++k) { S[3 * i + k] = r[3 + i] * nh[k]; S[9 + 3 * k + i] = p1[k] * h[i]; }
+      C8_UNROLL
+      for (int i = 0; i < 3; ++i) { S[18 + i] = -r[i] * Nm; S[21 + i] = -r[7] * h[i]; }
+      S[24] = fma(rho, gh, r[7] * Nm);
+    } else {
+      C8_UNROLL
+      for (int i = 0; i < 3; ++i)
+        C8_UNROLL
+        for (int k = 0; k < 3; ++k) {
+          S[3 * i + k] = fma(r[3 + i], nh[k], S[3 * i + k]);
+          S[9 + 3 * k + i] = fma(p1[k], h[i], S[9 + 3 * k + i]);
+        }
+      C8_UNROLL
+      for (int i = 0; i < 3; ++i) { S[18 + i] = fma(-r[i], Nm, S[18 + i]); S[21 + i] = fma(-r[7], h[i], S[21 + i]); }
+      S[24] = fma(rho, gh, fma(r[7], Nm, S[24]));
+    }
+  }
+  // J[4 i + k] = block entry (row i of the row node, column k of the column node; 3 = p) from the sums over the points
+  C8_HD static void closed_form_block_finish(double const* S, double inv_kappa, double* J) {
+    double const* const X = S + 9;
+    double const tr = X[0] + X[4] + X[8];
+    C8_UNROLL
+    for (int i = 0; i < 3; ++i)
+      C8_UNROLL
+      for (int k = 0; k < 3; ++k) {
+        double const v = S[3 * i + k] + fma(-2. / 3., X[3 * i + k], X[3 * k + i]);
+        J[4 * i + k] = (i == k) ? v + tr : v;
+      }
+    C8_UNROLL
+    for (int i = 0; i < 3; ++i) { J[4 * i + 3] = S[18 + i]; J[12 + i] = S[21 + i]; }
+    J[15] = -(S[24] * inv_kappa);
   }
 };
 template <class T> struct SmallJ2 : SmallJ2Dim<T, 3> {};       // "small_J2" on a 3-D mesh

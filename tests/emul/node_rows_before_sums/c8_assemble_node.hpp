@@ -7,7 +7,7 @@
 // the four CSR rows (u_0, u_1, u_2, p) of one node, forms them from the node's (up to eight) elements and writes each
 // row once.  No stage, no atomics on global memory, every sum in a fixed order: bitwise reproducible.
 //
-// What makes it affordable is the model's closed form (Model::closed_form, Model::closed_form_row / _block_sums): the
+// What makes it affordable is the model's closed form (Model::closed_form, Model::closed_form_row / _block): the
 // tangent data of a point are a handful of doubles, so the eight nodes of an element each recompute them (on all 64
 // lanes at once, one lane per (element, point)) instead of sharing them through memory, and the contraction with
 // the shape functions -- the bulk of the arithmetic -- is split over the nodes without redundancy: every 4 x 4
@@ -24,10 +24,7 @@
 //            Lane l of an element owns point hex_code(l), not point l (phase B, below); the eight lanes still read 64
 //            contiguous bytes per load, and per point nothing changes
 //   phase B  lane = (element s of the node, column node m)   the 4 x 4 block d R_(node,.) / d x_(m,.) summed over the
-//            element's eight points.  The sum comes first and the combination of its terms after it: a point adds to the 25
-//            sums of Model::closed_form_block_sums, closed_form_block_finish forms the 16 entries from them once, after the
-//            eighth point (the three "a" terms of the (u, u) entries are entries of ONE 3 x 3 matrix summed over the points;
-//            c8_models.hpp).  No load and no table: dN_m/dx at a point is G(pt)^T dN_m/dxi(pt); the
+//            element's eight points: 16 accumulators.  No load and no table: dN_m/dx at a point is G(pt)^T dN_m/dxi(pt); the
 //            lane that holds G(pt) since phase A forms it for the lane that needs it at that step, and a register exchange
 //            inside the group of eight lanes (lane_xor8: DPP moves on the GPU) delivers the three doubles.  With the points
 //            owned as above, step c pairs lane l with lane l ^ c and the reference gradient is a constant of the step
@@ -77,7 +74,7 @@ template <class E, class ModelD, int MAXDEG, bool MANY> struct NodeShared {
   alignas(16) double nodal[8][E::NN][4];    // (u_0, u_1, u_2, p) of the nodes of the eight elements, loaded one node per lane
   double nshape[8];                         // N of the reference element by agreement pattern of node and point (hex_pattern)
                                             // (forward assembly; the struct has no ADJ parameter, the adjoint leaves it unused)
-  double el[8][2];                          // per element: the model's per-element scalars (closed_form_block_scalars)
+  double el[8][2];                          // per element: the model's per-element scalars (closed_form_row)
   double bsum[4];
   C8_HD double* rec(int s, int pt) { return buf + (s * E::NP0 + pt) * LDR; }
   C8_HD double* img() { return buf + (MANY ? NREC : 0); }  // img00 starts here, the others at:
@@ -329,10 +326,6 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       for (int c = 0; c < 9; ++c) r.G[c] = ((pt >> (c / 3)) & 1) ? G[c] : -G[c];
       typename Model::ClosedForm cf;
       Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, r.h, ms.stab_mult, cf, true);
-      // phase B's scalars of the element (tau kappa, 1 / kappa), formed here, from the parameters the closed form has just
-      // read: behind the store below they would be fetched again
-      double esc[2];
-      Model::closed_form_block_scalars(mt.params + (size_t)es * Model::NPARAMS, cf.t, esc);
       if (!ADJ && a == 0) {  // local->scatter (local_residual.cpp:624-631): once per element, by the wavefront of its first node
         C8_UNROLL
         for (int j = 0; j < NL; ++j) fa.xi[q0 + j] = cf.xi[j];
@@ -345,7 +338,7 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       double* const rc = sh.rec(s, pt);
       double el[2];
       Model::template closed_form_row<ADJ>(cf.t, w, g, Na, rc, el);
-      if (pt == 0) { sh.el[s][0] = esc[0]; sh.el[s][1] = esc[1]; }
+      if (pt == 0) { sh.el[s][0] = el[0]; sh.el[s][1] = el[1]; }
       if constexpr (!ADJ) {
         // the point's share of R_(node,.): fluxes contracted with the row node's shape entries
         C8_UNROLL
@@ -380,13 +373,11 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       auto& r = ex.lane(lane_);
       int lane = lane_;
       C8_PIN(lane);
-      if (!r.valid) return;  // a lane without an element has no block: phase C passes it over (s >= ne), J is not read
+      C8_UNROLL
+      for (int j = 0; j < 16; ++j) r.J[j] = 0.;
+      if (!r.valid) return;
       int const s = lane >> 3, m = lane & 7;
-      // The sums over the element's eight points the block is a fixed combination of (Model::closed_form_block_sums), combined
-      // once after the last step (closed_form_block_finish): the three "a" terms of the (u, u) entries are entries of ONE 3 x 3
-      // matrix X summed over the points, so a step accumulates X and the b term's C, not the nine combined entries
-      double S[Model::NSUM];
-      double const rho = sh.el[s][0];  // tau kappa (phase A2); 1 / kappa is read after the last step
+      double const el[2] = {sh.el[s][0], sh.el[s][1]};
       // dN_m/dx of this lane's column node from the inverse Jacobians the element's lanes hold since phase A2, no table.  At
       // step c the lane takes the point of lane l ^ c, pt = hex_code(l) ^ hex_code(c): node m = l agrees with that point on
       // the axes hex_code(c) ^ 7 -- the same pattern in every lane, so N_m(pt) and |dN_m/dxi_k| are constants of the step.
@@ -404,20 +395,17 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
             double const* const Gs = ex.lane(l).G;
             return k0 * Gs[d] + k1 * Gs[3 + d] + k2 * Gs[6 + d];
           });
-        // step 0 starts the sums (no zeroing moves).  A zero sum may then be -0 where adding to +0 gave +0; phase C adds the
-        // block to an image that starts at +0, and (+0) + (-0) = +0: the stored values are the same
-        Model::template closed_form_block_sums<c == 0>(sh.rec(s, hex_code(m) ^ hc), rho, h, v[0], S);
+        Model::closed_form_block(sh.rec(s, hex_code(m) ^ hc), el, h, v[0], r.J);
         // one point's record in registers at a time: without the lines below the compiler fetches the records of all
         // eight points first (over a hundred doubles) and spills
         C8_UNROLL
-        for (int j = 0; j < Model::NSUM; ++j) C8_PIN(S[j]);
+        for (int j = 0; j < 16; ++j) C8_PIN(r.J[j]);
         C8_SCHED_FENCE();
       };
       step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{});
       step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 3>{});
       step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
       step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{});
-      Model::closed_form_block_finish(S, sh.el[s][1], r.J);
       if (m < 4) {
         double v = 0.;
         C8_UNROLL
