@@ -402,13 +402,17 @@ def check_adjoint_chain(orc, dut, c, model, eps, tol, history="proportional", k5
         assert abs(dut.eval_qoi(u, p) - orc.eval_qoi(u, p)) < tol * max(1.0, abs(orc.eval_qoi(u, p)))
 
 
-def check_two_element_sets(factory, kind, tol, wave=None):
+def check_two_element_sets(factory, kind, tol, wave=None, mesh=None):
     """Two material blocks with different parameters and different active-parameter lists
-    (local_residual.cpp:96-100 per-set parameters, :812-819 seed_wrt_params(es), :859-867 scatter_es_gradient)."""
-    et, c, conn = mesh_of(kind)
-    nelems = len(conn)
+    (local_residual.cpp:96-100 per-set parameters, :812-819 seed_wrt_params(es), :859-867 scatter_es_gradient).
+    mesh = (element type, coords, conn, element set): that mesh and set instead of mesh_of(kind) and a drawn set."""
     rng = np.random.default_rng(21)
-    es = (rng.random(nelems) < 0.4).astype(np.int32)  # ragged: sets are interleaved, not contiguous
+    if mesh is None:
+        et, c, conn = mesh_of(kind)
+        es = (rng.random(len(conn)) < 0.4).astype(np.int32)  # ragged: sets are interleaved, not contiguous
+    else:
+        et, c, conn, es = mesh
+        rng.random(len(conn))  # (the draws below stay the ones of the default mesh)
     params = [[1000.0, 0.25, 100.0, 2.0, 0.0, 0.0], [700.0, 0.3, 50.0, 1.2, 1e-4, 5.0]]
     orc = ol.Oracle(et, c, conn, "small_J2", params, elem_set=es)
     dut = factory(et, c, conn, "small_J2", params, elem_set=es)

@@ -64,6 +64,12 @@ def _hex(n, jig=0.0):
     return np.ascontiguousarray(meshes.jiggle(c, sets, jig) if jig else c), conn
 
 
+def _renumbered(mesh_, seed):
+    import renumber_cases
+    c, conn, _, _ = renumber_cases.renumber(mesh_[0], mesh_[1], seed)
+    return c, conn
+
+
 def _tri(nx, ny, jig=0.0):
     c, conn, sets = meshes.tri_mesh(nx, ny)
     return np.ascontiguousarray(meshes.jiggle_2d(c, sets, jig) if jig else c), conn
@@ -82,6 +88,9 @@ _MAKERS = {
     "brick221": lambda: (HEX8,) + meshes.brick(2, 2, 1)[:2], "tet223": lambda: (TET4,) + tet_split((2, 2, 3)),
     "tri73": lambda: (TRI3,) + _tri(7, 3), "tri102": lambda: (TRI3,) + _tri(10, 2),
     "brick3_jiggled": lambda: (HEX8,) + _hex(3, 0.05), "tri33_jiggled": lambda: (TRI3,) + _tri(3, 3, 0.05),
+    # random node ids, random element order, a random rotation of every element's local nodes (renumber_cases.py)
+    "brick3_jiggled_renumbered": lambda: (HEX8,) + _renumbered(_hex(3, 0.05), 31),
+    "pinched_bricks_renumbered": lambda: (HEX8,) + _renumbered(meshes.pinched_bricks(), 32),
 }
 TABLE = ("brick1", "brick2", "brick3", "pinched_bricks", "tet1", "tet2", "tet3", "tri11", "tri22", "tri33", "tri61", "fan", "tet3_jiggled")
 HOPELESS = ("tet1", "tri11")
