@@ -63,6 +63,17 @@ static int upload_active(c8_ctx* c) {
   return C8_OK;
 }
 
+// The closed form's per-set constants (MeshTables::cf_const) from the device parameters, for the models whose row-per-node
+// kernels read them: called wherever d_params is written, on the context's stream behind the copy.
+static int fill_constants(c8_ctx* c) {
+  if (!c->ks.closed_form_constants) return C8_OK;
+  int const nsets = c->mesh.nsets;
+  if (!c->d_cf_const) C8_HIP(hipMalloc((void**)&c->d_cf_const, (size_t)nsets * c->ks.num_constants * sizeof(double)));
+  C8_HIP(c->ks.closed_form_constants(c->d_params, c->d_cf_const, nsets, c->stream));
+  C8_HIP(hipStreamSynchronize(c->stream));  // the stream may be another one by the next assembly (c8_set_stream)
+  return C8_OK;
+}
+
 extern "C" {
 
 const char* c8_last_error(void) { return g_c8_last_error.c_str(); }
@@ -147,7 +158,7 @@ int c8_create(const c8_mesh_desc* md, const c8_model_desc* mo, c8_ctx** out) {
       (rc = upload(&c->d_nodeptr, c->graph.nodeptr)) || (rc = upload(&c->d_nodeadj, c->graph.nodeadj)) || (rc = upload(&c->d_pos, c->graph.pos)) ||
       (rc = upload(&c->d_elem_set, c->mesh.elem_set)) || (rc = upload(&c->d_order, c->order)) ||
       (rc = upload(&c->d_nodeelem_ptr, c->graph.nodeelem_ptr)) || (rc = upload(&c->d_nodeelem, c->graph.nodeelem)) ||
-      (rc = upload(&c->d_params, c->params)) || (rc = upload_active(c))) {
+      (rc = upload(&c->d_params, c->params)) || (rc = fill_constants(c)) || (rc = upload_active(c))) {
     c8_destroy(c);
     return rc;
   }
@@ -199,7 +210,7 @@ void c8_destroy(c8_ctx* c) {
   for (hipEvent_t e : c->ev_asm) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_sum) (void)hipEventDestroy(e);
   if (c->sum_stream) (void)hipStreamDestroy(c->sum_stream);
-  void* bufs[] = {c->d_qoi_rec, c->d_qoi_part, c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
+  void* bufs[] = {c->d_qoi_rec, c->d_qoi_part, c->d_vfm_part, c->d_shape,c->d_cal_faces, c->d_cal_S, c->d_nodeelem_ptr, c->d_nodeelem, c->d_nodeadj, c->d_scalar, c->d_xi_saved, c->d_work[0], c->d_work[1], c->d_work[2], c->d_work[3], c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, c->d_order, c->d_params, c->d_cf_const, c->d_active, c->d_status, c->d_nn, c->d_nn_part, c->d_kry_minv, c->d_kry_vec, c->d_kry_part, c->d_kry_scalars, c->d_kry_list, c->d_kry_sums, c->d_kry_colors, c->d_kry_agg, c->d_kry_agg_off, c->d_kry_cflags, c->d_kry_Ac, c->d_kry_cvec, c->d_kry_ipiv, c->d_kry_pc_agg, c->d_kry_pc_off, c->d_kry_pc_flags, c->d_kry_pc_imp};
   for (void* b : bufs) (void)hipFree(b);
   c8_krylov_release(c);
   c8_spr_release(c);
@@ -237,6 +248,8 @@ int c8_set_params(c8_ctx* c, const double* params) {
   if (!c || !params) return fail(C8_ERR_ARG, "c8_set_params: bad argument");
   c->params.assign(params, params + c->params.size());
   C8_HIP(hipMemcpyAsync(c->d_params, c->params.data(), c->params.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  int const rc = fill_constants(c);
+  if (rc) return rc;
   C8_HIP(hipStreamSynchronize(c->stream));
   return C8_OK;
 }
@@ -307,7 +320,7 @@ int c8_gather_finish(c8_ctx* c) {
   c->gather_pending = false;
   if (c->pending_node_rows) {
     c->pending_node_rows = false;
-    MeshTables const mt{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, nullptr, c->d_params, c->d_shape};
+    MeshTables const mt{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, nullptr, c->d_params, c->d_shape, nullptr, c->d_cf_const};
     AdjointArgs const* const paa = c->pending_adjoint ? &c->pending_aa : nullptr;
     C8_HIP(c->ks.node_rows(mt, c->ms, c->pending_fa, paa, c->pending_ga, 0, c->early_begin, c->graph.max_degree, c->graph.max_node_elems, c->stream));
     C8_HIP(c->ks.node_rows(mt, c->ms, c->pending_fa, paa, c->pending_ga, c->early_end, c->mesh.nnodes - c->early_end, c->graph.max_degree, c->graph.max_node_elems, c->stream));
@@ -404,7 +417,7 @@ static int run_node_rows(c8_ctx* c, FieldArgs const& fa, SystemArgs const& sa, A
   if (c->gather_pending) return fail(C8_ERR_ARG, "row-per-node assembly: c8_gather_finish has not been called for the previous assembly");
   GatherArgs ga{c->d_nodeptr, c->d_pos, c->d_nodeelem_ptr, c->d_nodeelem, nullptr, 0, nullptr,
                 {{sa.A[0][0], sa.A[0][1]}, {sa.A[1][0], sa.A[1][1]}}, {sa.b[0], sa.b[1]}, c->assign_mode};
-  MeshTables const mt{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, nullptr, c->d_params, c->d_shape};
+  MeshTables const mt{c->d_conn, c->d_coords, c->d_nodeptr, c->d_pos, c->d_elem_set, nullptr, c->d_params, c->d_shape, nullptr, c->d_cf_const};
 #ifdef C8_STAMPS
   if (!c->d_stamps) C8_HIP(hipMalloc((void**)&c->d_stamps, 4096 * 16 * sizeof(unsigned long long)));
   ga.stamps = c->d_stamps;

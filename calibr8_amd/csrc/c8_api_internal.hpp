@@ -94,6 +94,7 @@ struct c8_ctx {
   c8::AdjointArgs pending_aa{};
   double* d_shape = nullptr;          // cached shape tables of the wave kernels, [nelems][ks.shape_stride] (hex8; null: computed per call)
   double* d_params = nullptr;
+  double* d_cf_const = nullptr;  // [nsets][ks.num_constants]: MeshTables::cf_const, refilled whenever d_params is written (fill_constants)
   int32_t* d_active = nullptr;  // [nsets][10]: {grad offset, n_active, indices...}
   int* d_status = nullptr;
   unsigned long long* d_stamps = nullptr;  // -DC8_STAMPS diagnostic build only

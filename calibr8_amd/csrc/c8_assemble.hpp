@@ -45,6 +45,10 @@ struct MeshTables {
   // dN/dx, w dv and the element size are computed once per context (store_shape_tables) instead of per call
   double const* shape = nullptr;
   double const* nn = nullptr;  // the embedded network of hybrid_hyper_J2_plane_stress (c8_models.hpp: nn_value_slope), or null
+  // [nsets][Model::NCONST], 16-byte aligned: what the model's closed form computes from the parameters alone
+  // (Model::closed_form_constants), filled on the device wherever the device parameters are written; read by the
+  // row-per-node kernels on the device, null elsewhere
+  double const* cf_const = nullptr;
 };
 struct ModelSettings {
   double stab_mult;

@@ -93,6 +93,29 @@ template <class Lane> struct GpuExec {
     }
     return __hiloint2double(hi, lo);
   }
+  // Range-checked row I/O (row_load / row_store, c8_assemble_node.hpp): entry j of a row of n doubles at base through a buffer
+  // descriptor over exactly those 8 n bytes.  The address unit checks the range: a lane with j >= n loads 0 and its store is
+  // dropped -- no compare, no exec-mask region, no 64-bit address per lane.  base and n must be wave-uniform and PROVABLY so
+  // (kernel arguments, blockIdx, values loaded through them): the descriptor then stays in scalar registers and is built once
+  // for the accesses of a phase that share it; from a per-lane value the compiler would wrap every access in a
+  // v_readfirstlane loop.  0 <= j, 8 j < 2^31.
+  using has_row_io = void;
+  using has_const_table = void;  // the library fills MeshTables::cf_const (k_closed_form_constants, c8_api.hip)
+  __device__ __forceinline__ static auto row_rsrc(double const* base, int n) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, 8 * n, 0x00020000);  // raw buffer, 32-bit data format
+  }
+  __device__ __forceinline__ double row_load(double const* base, int n, int j) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    v2u const v = __builtin_amdgcn_raw_buffer_load_b64(row_rsrc(base, n), 8 * j, 0, 0);
+    return __hiloint2double((int)v[1], (int)v[0]);
+  }
+  __device__ __forceinline__ void row_store(double* base, int n, int j, double x) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    v2u v;
+    v[0] = (unsigned)__double2loint(x);
+    v[1] = (unsigned)__double2hiint(x);
+    __builtin_amdgcn_raw_buffer_store_b64(v, row_rsrc(base, n), 8 * j, 0, 0);
+  }
   // get(l) of lane l ^ 32 (the other half of the wavefront)
   template <class F> __device__ __forceinline__ double xor32(int lane, F get) { return __shfl_xor(get(lane), 32); }
   // lanes 0..31: getA(lane) + getA(lane + 32); lanes 32..63: getB(lane - 32) + getB(lane).  v_permlane32_swap (gfx950)
@@ -496,7 +519,13 @@ template <class E> static hipError_t launch_gather_rows(GatherArgs const& ga, in
 // combines the terms of the block once, after the eighth point (Model::closed_form_block_sums / _finish: 41 operations per
 // step and 24 at the end instead of 59 per step; 111 of 868 FP64 instructions less in K1, 128 registers, four wavefronts
 // per SIMD as before): 3.15-3.16 / 3.65-3.66 ms beside 3.35-3.36 / 3.79-3.82 ms in one call (last part;
-// profiles/README.md, sums_*).
+// profiles/README.md, sums_*).  The rows now go in and out through one buffer descriptor per CSR block (GpuExec::row_load /
+// row_store: the address unit checks the range, no compare, exec-mask region or 64-bit address per lane), the accumulator is
+// zeroed whole in 16-byte LDS writes, and K1 reads what the closed form computes from the parameters alone from a table per
+// element set (MeshTables::cf_const, k_closed_form_constants) instead of forming five reciprocals at every point: 1 767 ->
+// 1 525 static instructions in the lean K1 (FP64 763 -> 722, other vector ALU 418 -> 313, scalar 403 -> 313), the same
+// bits: 2.98-3.01 / 3.53-3.60 ms beside 3.07-3.11 / 3.57-3.66 ms in one call (last part; profiles/README.md,
+// rowio_*).
 #ifndef C8_NODE_WAVES
 #define C8_NODE_WAVES 3
 #endif
@@ -544,6 +573,7 @@ static hipError_t launch_node_rows(MeshTables const& mt, ModelSettings const& ms
     hipLaunchKernelGGL((k_node_rows_update_g<E, ModelT>), dim3((unsigned)((npoints + 255) / 256)), dim3(256), 0, stream, mt, *aa, npoints);
     return hipGetLastError();
   }
+  if (!mt.cf_const) return hipErrorInvalidValue;  // the kernels read the closed form's constants there
   int const nblocks = count;
   int const grid = stripe_grid(nblocks, NODE_STRIPE);
   bool const lean = max_degree <= 32 && max_node_elems <= 8;
@@ -557,14 +587,31 @@ static hipError_t launch_node_rows(MeshTables const& mt, ModelSettings const& ms
   }
   return hipGetLastError();
 }
+// The closed form's per-set constants (Model::closed_form_constants; MeshTables::cf_const): one lane per element set.  On the
+// device, not on the host: c8_rcp is v_rcp_f64 and two Newton steps here and 1 / x there.
+template <template <class> class ModelT>
+__global__ void __launch_bounds__(64) k_closed_form_constants(double const* params, double* table, int nsets) {
+  using Model = ModelT<Dual>;
+  int const es = blockIdx.x * 64 + threadIdx.x;
+  if (es < nsets) Model::closed_form_constants(params + (size_t)es * Model::NPARAMS, table + (size_t)es * Model::NCONST);
+}
+template <template <class> class ModelT>
+static hipError_t launch_closed_form_constants(double const* params, double* table, int nsets, hipStream_t stream) {
+  hipLaunchKernelGGL((k_closed_form_constants<ModelT>), dim3((unsigned)((nsets + 63) / 64)), dim3(64), 0, stream, params, table, nsets);
+  return hipGetLastError();
+}
 template <class E, template <class> class ModelT, class = void> struct NodeKernel {
   static NodeRowsFn get() { return nullptr; }
+  static ConstantsFn get_constants() { return nullptr; }
+  static constexpr int NCONST = 0;
   static LaunchFn get_adjoint_local() { return nullptr; }
   static LaunchFn get_param_gradient() { return nullptr; }
 };
 template <template <class> class ModelT>
 struct NodeKernel<Elem<C8_HEX8>, ModelT, std::enable_if_t<has_closed_form_rows<ModelT<Dual>>::value>> {
   static NodeRowsFn get() { return &launch_node_rows<Elem<C8_HEX8>, ModelT>; }
+  static ConstantsFn get_constants() { return &launch_closed_form_constants<ModelT>; }
+  static constexpr int NCONST = ModelT<Dual>::NCONST;
   static LaunchFn get_adjoint_local() { return &launch_adjoint_local_closed<Elem<C8_HEX8>, ModelT>; }
   static LaunchFn get_param_gradient() { return &launch_param_gradient_closed<Elem<C8_HEX8>, ModelT>; }
 };
@@ -804,6 +851,8 @@ template <class E, template <class> class ModelT> static KernelSet kernel_set(Mo
   ks.shape_stride = SHAPE_STRIDE;
   ks.gather_rows = &launch_gather_rows<E>;
   ks.node_rows = NodeKernel<E, ModelT>::get();
+  ks.closed_form_constants = NodeKernel<E, ModelT>::get_constants();
+  ks.num_constants = NodeKernel<E, ModelT>::NCONST;
   ks.adjoint_local_closed = NodeKernel<E, ModelT>::get_adjoint_local();
   ks.param_gradient_closed = NodeKernel<E, ModelT>::get_param_gradient();
   ks.stage_stride = stage_stride<E>();

@@ -28,6 +28,9 @@ typedef hipError_t (*NodeRowsFn)(MeshTables const&, ModelSettings const&, FieldA
 // the VFM kernels (c8_assemble_vfm.hpp): the whole mesh in one launch, one partial sum per output and block into part
 typedef hipError_t (*VfmFn)(LaunchArgs const&, VfmArgs const&, double* part);
 
+// the closed form's per-set constants from the device parameters (Model::closed_form_constants): table[nsets][num_constants]
+typedef hipError_t (*ConstantsFn)(double const* params, double* table, int nsets, hipStream_t);
+
 struct KernelSet {
   LaunchFn forward_jacobian;   // K1, one lane group (NDOF lanes) per element
   LaunchFn forward_jacobian_wave;  // K1, one wavefront per element (hex8 only, else null)
@@ -55,6 +58,10 @@ struct KernelSet {
   VfmFn vfm_forward_sens = nullptr;  // FS
   VfmFn vfm_adjoint = nullptr;       // A
   int vfm_groups_per_block = 0;      // element groups per block of those kernels (blocks = partial sums per output)
+  // the row-per-node kernels read the closed form's parameter-only values from a table (MeshTables::cf_const): its filling
+  // kernel and the doubles per element set; null / 0 where node_rows is null
+  ConstantsFn closed_form_constants = nullptr;
+  int num_constants = 0;
 };
 
 // the weight gradient of the embedded network (c8_assemble_nn.hpp): the partial rows of nn_grad_blocks(npts) blocks,

@@ -34,10 +34,7 @@
 //   phase C  blocks added into the node's row accumulator in LDS, every entry summed in ascending element order.  The
 //            accumulator is an IMAGE of the node's four CSR row blocks, entry for entry in their order (NodeShared::img*)
 //   phase D  the finished rows added to (or assigned to) the four CSR blocks -- four straight copies, lane j + 64 it
-//            takes entry j + 64 it of a block -- the residual entries to b.  The old values are fetched before phase C and
-//            the sums stored here through range-checked accesses (row_load / row_store): a lane past the end of a block's
-//            row reads 0 and writes nothing, so neither side has a bound to compare against or a branch around the access.
-//            Assign mode reads rows of length zero
+//            takes entry j + 64 it of a block -- the residual entries to b
 //
 // Requires an element with 8 nodes, 8 coupled points and identical point sets for both ip sets (hex8), the cached
 // shape tables (c8_set_shape_cache: of an element's entry these kernels read the inverse Jacobians, the weights and the size,
@@ -132,24 +129,6 @@ template <int C, class EX, class F> C8_HD double lane_xor8(EX& ex, int lane, F g
   } else return get(lane ^ C);
 }
 
-// Entry j of a row of n doubles at base, both wave-uniform: row_load gives base[j] for j < n and 0 past the end, row_store
-// writes base[j] for j < n and nothing past the end.  An executor with range-checked memory accesses provides both (the GPU's:
-// a buffer descriptor over the row's 8 n bytes, the address unit does the check -- no compare, no exec-mask region and no 64-bit
-// address per lane); one without them, the CPU emulation for one, takes the guarded access.
-template <class EX, class = void> struct has_row_io : std::false_type {};
-template <class EX> struct has_row_io<EX, std::void_t<typename EX::has_row_io>> : std::true_type {};
-// an executor of the library, which keeps MeshTables::cf_const (the closed form's per-set constants) filled
-template <class EX, class = void> struct has_const_table : std::false_type {};
-template <class EX> struct has_const_table<EX, std::void_t<typename EX::has_const_table>> : std::true_type {};
-template <class EX> C8_HD double row_load(EX& ex, double const* base, int n, int j) {
-  if constexpr (has_row_io<EX>::value) return ex.row_load(base, n, j);
-  else return j < n ? base[j] : 0.;
-}
-template <class EX> C8_HD void row_store(EX& ex, double* base, int n, int j, double x) {
-  if constexpr (has_row_io<EX>::value) ex.row_store(base, n, j, x);
-  else if (j < n) base[j] = x;
-}
-
 // The reference hex8 at its Gauss points BY AGREEMENT PATTERN.  Node signs and point coordinates are +-1 and +-1/sqrt(3) per
 // axis, so N_m and dN_m/dxi at a point depend only on the set j of axes on which the node's sign equals the point's (bit k of
 // j):   N = v[0],   dN/dxi_k = s_k v[1 + k]   with s_k the node's sign along k,
@@ -209,17 +188,11 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
   int const n3 = 3 * deg;
   if (e0 == e1) return;  // a node without elements (phantom columns of a mesh part): its rows are not touched
   C8_NSTAMP(0);
-  // the whole accumulator, not the 16 deg doubles of this node's image: no compare and no exec-mask region, and a lane
-  // writes two neighbouring doubles at a time (16-byte LDS writes)
-  static_assert(SH::NACC % 128 == 0 && (SH::NREC % 2 == 0 || !MANY), "zero_acc: 64 lanes, 16 aligned bytes each");
-  // phase D reads the image up to 63 entries past its last block (row_store drops them): inside buf
-  static_assert(15 * MAXDEG + 64 <= (MANY ? SH::NACC : (SH::NREC > SH::NACC ? SH::NREC : SH::NACC)), "phase D reads inside buf");
   auto zero_acc = [&](int lane) {
     C8_UNROLL
-    for (int it = 0; it < SH::NACC / 128; ++it) {
-      double* const z = sh.img() + 2 * (lane + 64 * it);
-      z[0] = 0.;
-      z[1] = 0.;
+    for (int it = 0; it < (SH::NACC + 63) / 64; ++it) {
+      int const q = lane + 64 * it;
+      if (q < 16 * deg) sh.img()[q] = 0.;
     }
     if (lane < 4) sh.bsum[lane] = 0.;
   };
@@ -354,29 +327,12 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
       // the sign of node (lane & 7) along k (exact).  In the record: the lanes of the element read it there (lane_xor8)
       C8_UNROLL
       for (int c = 0; c < 9; ++c) r.G[c] = ((pt >> (c / 3)) & 1) ? G[c] : -G[c];
-      // what the closed form needs of the parameters alone (Model::closed_form_constants: 2 mu, kappa, four reciprocals, the
-      // thermal term): from the element set's row of the table the library keeps beside the device parameters, in 16-byte
-      // loads, where the executor says there is one; formed in place otherwise (the same expressions, the same values).  The
-      // adjoint assembly forms them in place as well: its other model functions go on reading the parameters, and with the
-      // table beside them K3 measured slower (132 registers for 130; DESIGN 3.8, last part)
-      double cst[Model::NCONST];
-      if constexpr (has_const_table<EX>::value && !ADJ) {
-        static_assert(Model::NCONST % 2 == 0, "rows of the table are read in 16-byte units");
-        struct alignas(16) Pair { double x, y; };
-        Pair const* const row = reinterpret_cast<Pair const*>(mt.cf_const) + (size_t)es * (Model::NCONST / 2);
-        C8_UNROLL
-        for (int k = 0; k < Model::NCONST / 2; ++k) {
-          Pair const v = row[k];
-          cst[2 * k] = v.x;
-          cst[2 * k + 1] = v.y;
-        }
-      } else Model::closed_form_constants(mt.params + (size_t)es * Model::NPARAMS, cst);
       typename Model::ClosedForm cf;
-      Model::closed_form_c(cst, q, xi_old, ms.abs_tol, r.h, ms.stab_mult, cf, true);
-      // phase B's scalars of the element (tau kappa, 1 / kappa), formed here, from the values the closed form has just
+      Model::closed_form(mt.params + (size_t)es * Model::NPARAMS, q, xi_old, ms.abs_tol, r.h, ms.stab_mult, cf, true);
+      // phase B's scalars of the element (tau kappa, 1 / kappa), formed here, from the parameters the closed form has just
       // read: behind the store below they would be fetched again
       double esc[2];
-      Model::closed_form_block_scalars_c(cst, cf.t, esc);
+      Model::closed_form_block_scalars(mt.params + (size_t)es * Model::NPARAMS, cf.t, esc);
       if (!ADJ && a == 0) {  // local->scatter (local_residual.cpp:624-631): once per element, by the wavefront of its first node
         C8_UNROLL
         for (int j = 0; j < NL; ++j) fa.xi[q0 + j] = cf.xi[j];
@@ -478,17 +434,20 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
         auto& r = ex.lane(lane_);
         int lane = lane_;
         C8_PIN(lane);  // what follows is derived from the lane number here, not at the top of the kernel and kept in registers
-        // range-checked loads (row_load): entry j of a block's row where the row has one, 0 past its end -- and everywhere in
-        // assign mode, whose rows have no entries to read
-        int const ld = ga.assign ? 0 : deg;
         C8_UNROLL
-        for (int it = 0; it < NL_::N00; ++it) r.a00[it] = row_load(ex, ga.A[0][0] + np * 9, 9 * ld, lane + 64 * it);
+        for (int it = 0; it < NL_::N00; ++it) {
+          int const j = lane + 64 * it;
+          r.a00[it] = 0.;
+          if (!ga.assign && j < 9 * deg) r.a00[it] = ga.A[0][0][np * 9 + j];
+        }
         C8_UNROLL
         for (int it = 0; it < NL_::N01; ++it) {
-          r.a01[it] = row_load(ex, ga.A[0][1] + np * 3, 3 * ld, lane + 64 * it);
-          r.a10[it] = row_load(ex, ga.A[1][0] + np * 3, 3 * ld, lane + 64 * it);
+          int const j = lane + 64 * it;
+          r.a01[it] = r.a10[it] = 0.;
+          if (!ga.assign && j < n3) { r.a01[it] = ga.A[0][1][np * 3 + j]; r.a10[it] = ga.A[1][0][np * 3 + j]; }
         }
-        r.a11 = row_load(ex, ga.A[1][1] + np, ld, lane);
+        r.a11 = 0.;
+        if (!ga.assign && lane < deg) r.a11 = ga.A[1][1][np + lane];
         r.bold = 0.;
         if (!ga.assign && lane < 4) r.bold = lane < 3 ? ga.b[0][(size_t)node * 3 + lane] : ga.b[1][node];
       });
@@ -554,20 +513,20 @@ C8_HD void node_rows_closed(EX& ex, NodeShared<E, ModelT<Dual>, MAXDEG, MANY>& s
     C8_PIN(r.bold);
     // the image is in the blocks' own order: entry j of a block is entry j of its image
     double const* const i00 = sh.img(), * const i01 = i00 + SH::img01(deg), * const i10 = i00 + SH::img10(deg), * const i11 = i00 + SH::img11(deg);
-    // range-checked stores (row_store): a lane past the end of a block's row writes nothing.  Such a lane has read the image
-    // past that block's part -- inside NodeShared::buf (the assertion beside zero_acc) --, a value that goes nowhere
     C8_UNROLL
     for (int it = 0; it < NL_::N00; ++it) {
       int const j = lane + 64 * it;
-      row_store(ex, ga.A[0][0] + np * 9, 9 * deg, j, r.a00[it] + i00[j]);
+      if (j < 9 * deg) ga.A[0][0][np * 9 + j] = r.a00[it] + i00[j];
     }
     C8_UNROLL
     for (int it = 0; it < NL_::N01; ++it) {
       int const j = lane + 64 * it;
-      row_store(ex, ga.A[0][1] + np * 3, n3, j, r.a01[it] + i01[j]);
-      row_store(ex, ga.A[1][0] + np * 3, n3, j, r.a10[it] + i10[j]);
+      if (j < n3) {
+        ga.A[0][1][np * 3 + j] = r.a01[it] + i01[j];
+        ga.A[1][0][np * 3 + j] = r.a10[it] + i10[j];
+      }
     }
-    row_store(ex, ga.A[1][1] + np, deg, lane, r.a11 + i11[lane]);
+    if (lane < deg) ga.A[1][1][np + lane] = r.a11 + i11[lane];
     if (lane < 3) ga.b[0][(size_t)node * 3 + lane] = r.bold + sh.bsum[lane];
     if (lane == 3) ga.b[1][node] = r.bold + sh.bsum[3];
   });

@@ -228,35 +228,10 @@ template <class T, int DIM> struct SmallJ2Dim {
   // fuses the two ip sets of hex8; the lane-group kernels leave it to the loop over the second ip set
   C8_HD static void closed_form(double const* prm, double const* q, double const* xi_old, double abs_tol, double h,
                                 double stab_mult, ClosedForm& cf, bool pressure_mass) {
-    double c[NCONST];
-    closed_form_constants(prm, c);
-    closed_form_c(c, q, xi_old, abs_tol, h, stab_mult, cf, pressure_mass);
-  }
-  // What closed_form computes from the parameters alone, each value by the expression closed_form used for it: five
-  // reciprocals (v_rcp_f64 and two Newton steps each) that a kernel need not repeat at every point.  The values change with
-  // the parameters (c8_set_params), not from assembly to assembly: the library keeps them per element set beside the device
-  // parameters (MeshTables::cf_const, filled ON THE DEVICE -- c8_rcp is not the host's 1 / x) and the row-per-node kernels
-  // read them there.  2 mu and 1 / H stay separate values, as do kappa and the thermal term: a product formed ahead would
-  // round differently from the expression that multiplies them inside a larger one.
-  //   c: 2 mu | 1 / mu | kappa | 1 / kappa | 1 / H, H = 2 mu + 2K/3 | E cte dT / (1 - 2 nu) | K | Y
-  static constexpr int NCONST = 8;
-  C8_HD static void closed_form_constants(double const* prm, double* c) {
+    double const sqrt_23 = 0.81649658092772603273;
     double const E = prm[0], nu = prm[1], K = prm[2], Y = prm[3];
     double const mu = E * c8_rcp(2. * (1. + nu)), kappa = E * c8_rcp(3. * (1. - 2. * nu));
-    c[0] = 2. * mu;
-    c[1] = c8_rcp(mu);
-    c[2] = kappa;
-    c[3] = c8_rcp(kappa);
-    c[4] = c8_rcp(2. * mu + (2. / 3.) * K);
-    c[5] = prm[4] * prm[5] * E * c8_rcp(1. - 2. * nu);
-    c[6] = K;
-    c[7] = Y;
-  }
-  // closed_form from those values (c: closed_form_constants) and the point's data
-  C8_HD static void closed_form_c(double const* c, double const* q, double const* xi_old, double abs_tol, double h,
-                                  double stab_mult, ClosedForm& cf, bool pressure_mass) {
-    double const sqrt_23 = 0.81649658092772603273;
-    double const mu2 = c[0], inv_mu = c[1], kappa = c[2], inv_kappa = c[3], K = c[6], Y = c[7];
+    double const inv_mu = c8_rcp(mu);
     // q: grad u (row-major), p, grad p, u
     double eps[9];
     C8_UNROLL
@@ -270,7 +245,7 @@ template <class T, int DIM> struct SmallJ2Dim {
     C8_UNROLL
     for (int k = 0; k < 9; ++k) {
       double const dev = eps[k] - ((k == 0 || k == 4 || k == 8) ? th : 0.);
-      st[k] = mu2 * (dev - pold[k]);
+      st[k] = (2. * mu) * (dev - pold[k]);
       ss += st[k] * st[k];
     }
     double const smag = sqrt(ss);
@@ -287,7 +262,7 @@ template <class T, int DIM> struct SmallJ2Dim {
     for (int k = 0; k < 9; ++k) n[k] = 0.;
     cf.t[2] = 0.;
     if (plastic) {
-      double const inv_H = c[4];
+      double const inv_H = c8_rcp(2. * mu + (2. / 3.) * K);
       // inside the band |f0| < abs_tol the reference's iteration stops at its first test, before any step: the state stays
       // xi_old (dgam = 0, theta = 1) and the tangent is that of the plastic equations there, b = -4 mu^2 / H
       double const dgam = fabs(f0) < abs_tol ? 0. : excess * inv_H;
@@ -295,20 +270,21 @@ template <class T, int DIM> struct SmallJ2Dim {
       C8_UNROLL
       for (int k = 0; k < 9; ++k) n[k] = st[k] * inv;
       cf.t[2] = (n[0] + n[4] + n[8]) * (1. / 3.);
-      theta = 1. - mu2 * dgam * inv;
-      cf.t[1] = mu2 * (1. - mu2 * inv_H - theta);
+      theta = 1. - (2. * mu) * dgam * inv;
+      cf.t[1] = (2. * mu) * (1. - (2. * mu) * inv_H - theta);
       cf.xi[0] = xi_old[0] + dgam * n[0]; cf.xi[1] = xi_old[1] + dgam * n[1]; cf.xi[2] = xi_old[2] + dgam * n[2];
       cf.xi[3] = xi_old[3] + dgam * n[4]; cf.xi[4] = xi_old[4] + dgam * n[5]; cf.xi[5] = xi_old[5] + dgam * n[8];
       cf.xi[NSYM] = alpha_old + sqrt_23 * dgam;
     }
-    cf.t[0] = mu2 * theta;
+    cf.t[0] = (2. * mu) * theta;
+    double const inv_kappa = c8_rcp(kappa);
     double const tau = (stab_mult * 0.5 * h * h) * inv_mu;
     cf.t[3] = pressure_mass ? inv_kappa : 0.;
     cf.t[4] = tau;
     double const p = q[9];
     C8_UNROLL
     for (int k = 0; k < 9; ++k) cf.F[k] = theta * st[k] - ((k == 0 || k == 4 || k == 8) ? p : 0.);
-    double const hydro = kappa * tr - c[5];
+    double const hydro = kappa * tr - prm[4] * prm[5] * E * c8_rcp(1. - 2. * nu);
     cf.F[9] = pressure_mass ? -(hydro * inv_kappa) + -(p * inv_kappa) : -(hydro * inv_kappa);
     cf.F[10] = -(tau * q[10]); cf.F[11] = -(tau * q[11]); cf.F[12] = -(tau * q[12]);
   }
@@ -552,11 +528,6 @@ template <class T, int DIM> struct SmallJ2Dim {
   C8_HD static void closed_form_block_scalars(double const* prm, double const* t, double* es) {
     double const kappa = prm[0] * c8_rcp(3. * (1. - 2. * prm[1]));
     es[0] = t[4] * kappa;
-    es[1] = t[3];
-  }
-  // ... with kappa taken from closed_form_constants
-  C8_HD static void closed_form_block_scalars_c(double const* c, double const* t, double* es) {
-    es[0] = t[4] * c[2];
     es[1] = t[3];
   }
   // FIRST: the sums START with this point (assigned, not added to zero: a zero may come out as -0 where 0 + x gives +0)
